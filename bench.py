@@ -2,6 +2,7 @@
 """bench.py -- headline benchmark: strand-Gaussian training iterations per second (+ forward render ms/view).
 
   python bench.py --gpus N --steps K --warmup W [--workload north_star|c2|c3|c4|c5|tiny] [--scaling weak|strong]
+                  [--dump-outputs DIR]
 
 One *train iteration* is the reference's (train.py:133-204): lr update, ONE camera view, render + 2 more raster
 passes inside the losses (mask, orientation), backward through all three, densification statistics, Adam step.
@@ -112,7 +113,39 @@ def parse():
     ap.add_argument("--eager", action="store_true", help="eager dispatch of every kernel instead of replaying the captured HIP graph")
     ap.add_argument("--blocking", action="store_true",
                     help="reference-style forward (host reads num_rendered in every pass) instead of the async capacity mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write what the last timed step handed its caller -- its loss and the model "
+                         "state it updated in place -- as DIR/<name>.npy (dump_outputs; rank 0)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, loss):
+    """--dump-outputs: the outputs of the last timed step -- `loss` (the step's return value), every optimizer parameter under
+    its group's name, and the densification statistics the step accumulates -- as <name>.npy, float32 (float64 for anything
+    else); arrays without elements are left out.  Over DUMP_LIMIT_BYTES in all, every array keeps the same seeded sample of its rows (default_rng(0) over its row
+    count: the same rows in every run of the same arguments)."""
+    import numpy as np
+    import torch
+    arrays = {} if loss is None else {"loss": loss.detach().reshape(-1)}
+    for g_ in model.optimizer.param_groups:
+        for j, p in enumerate(g_["params"]):
+            arrays[g_["name"] if len(g_["params"]) == 1 else f"{g_['name']}_{j}"] = p.detach()
+    arrays.update(max_radii2D=model.max_radii2D, xyz_gradient_accum=model.xyz_gradient_accum, denom=model.denom)
+    # (a parameter without elements -- f_rest at SH degree 0, shape [P, 0, 3] -- holds no output: not written)
+    arrays = {name: t for name, t in arrays.items() if t.numel() > 0}
+    torch.cuda.synchronize()
+    size = lambda t: t.numel() * (4 if t.dtype == torch.float32 else 8)
+    frac = min(1.0, DUMP_LIMIT_BYTES / max(1, sum(size(t) for t in arrays.values())))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if frac < 1.0 and t.dim() > 0 and t.shape[0] > 1:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], max(1, int(t.shape[0] * frac)), replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
 
 
 def cpu_baseline(model, cam, threads, bg):
@@ -295,10 +328,24 @@ def launcher_command(args, argv, port=None):
             "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + rest
 
 
+def _render_node_opens(minor):
+    """Whether this process may open the DRM render node of a KFD GPU node (the HIP runtime leaves out the GPUs it cannot
+    open: a container given some of a node's devices still shows all of them in the topology).  Unknown minor: counted."""
+    if minor is None:
+        return True
+    try:
+        fd = os.open(f"/dev/dri/renderD{int(minor)}", os.O_RDWR | os.O_CLOEXEC)
+    except OSError:
+        return False
+    os.close(fd)
+    return True
+
+
 def visible_gpus():
     """GPUs this process would see, counted WITHOUT a HIP call (the launcher must not initialise the runtime: it only starts the
-    ranks): the KFD topology's nodes with SIMDs, cut down by HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES.  None: unknown (no
-    topology to read although the driver is there) -- the ranks themselves refuse a world larger than their device count."""
+    ranks): the KFD topology's nodes with SIMDs that this process may read and whose render node it may open, cut down by
+    HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES.  None: unknown (no topology to read although the driver is there) -- the ranks
+    themselves refuse a world larger than their device count."""
     import glob
     n = 0
     if not os.path.isdir("/sys/class/kfd"):
@@ -309,9 +356,9 @@ def visible_gpus():
     for f in nodes:
         try:
             props = dict(line.split()[:2] for line in open(f) if len(line.split()) >= 2)
-            n += int(props.get("simd_count", "0")) > 0
         except OSError:
-            return None
+            continue                                     # a node this process may not read is not one it can use
+        n += int(props.get("simd_count", "0")) > 0 and _render_node_opens(props.get("drm_render_minor"))
     for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
         v = os.environ.get(var)
         if v is not None:
@@ -440,10 +487,10 @@ def main():
             raise SystemExit(f"--global-views {args.global_views} does not divide over {world} ranks")
         views_per_rank = args.global_views // world
     views_per_step = views_per_rank * world if strong else world      # views of ONE optimizer step, whole job
-    def measure(it_start, do_sustained, do_kernels):
+    def measure(it_start, do_sustained, do_kernels, dump_dir=None):
         """The measurement protocol on the model's CURRENT state: capture, W warm-up steps, `repeats` regions of EXACTLY K
-        steps each restarted from the post-warm-up state, the sustained leg, per-kernel HIP-event timing.  Leaves the
-        model in the post-warm-up state."""
+        steps each restarted from the post-warm-up state, (dump_dir: the outputs of the last timed step,) the sustained leg,
+        per-kernel HIP-event timing.  Leaves the model in the post-warm-up state."""
         it = it_start
         views = fused = None
         if fused_step_applicable(model, opt):
@@ -462,29 +509,35 @@ def main():
             def one_step():
                 nonlocal it
                 it += 1
-                gs.step(sampler.next_batch(args.global_views) if views_per_rank > 1 else sampler.next(), it)
+                return gs.step(sampler.next_batch(args.global_views) if views_per_rank > 1 else sampler.next(), it)
         else:
             def one_step():
                 nonlocal it
                 it += 1
-                training_step(model, sampler.next(), opt, bg, it, extent=extent, vp=vp, fused=fused)
+                return training_step(model, sampler.next(), opt, bg, it, extent=extent, vp=vp, fused=fused)[0]
 
         def run_steps(n_steps):
-            """EXACTLY n_steps optimizer steps: whole launches of the several-steps graph, the rest one step per launch."""
+            """EXACTLY n_steps optimizer steps: whole launches of the several-steps graph, the rest one step per launch.
+            Returns the (device) loss of the last one."""
             nonlocal it
+            loss = None
             K = gs.steps_per_graph if use_graph else 1
             while K > 1 and n_steps >= K:
-                gs.step_many([sampler.next() for _ in range(K)], it + 1)
+                loss = gs.step_many([sampler.next() for _ in range(K)], it + 1)[-1]
                 it += K
                 n_steps -= K
             for _ in range(n_steps):
-                one_step()
+                loss = one_step()
+            return loss
+
+        last_loss = None
 
         def timed_region(n_steps):
             """EXACTLY n_steps optimizer steps between two barrier + synchronize pairs; seconds, maximum over the ranks."""
+            nonlocal last_loss
             sync_all()
             t0 = time.perf_counter()
-            run_steps(n_steps)
+            last_loss = run_steps(n_steps)
             sync_all()
             t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
             if world > 1:
@@ -519,6 +572,8 @@ def main():
         for _ in range(max(1, args.repeats)):
             restore()
             regions.append(timed_region(args.steps))
+        if dump_dir is not None and rank == 0:
+            dump_outputs(dump_dir, model, last_loss)
         regions.sort()
         dt = regions[len(regions) // 2]
         sustained = None
@@ -575,7 +630,7 @@ def main():
                     inline_adam=bool(use_graph and gs.inline_adam),
                     collective_captured=(gs.collective_captured if use_graph else False))
 
-    head = measure(0, args.sustained_seconds > 0, not args.no_kernel_timing)
+    head = measure(0, args.sustained_seconds > 0, not args.no_kernel_timing, dump_dir=args.dump_outputs)
     dt, regions, sustained, kern, kern_steps, fused = (head[k] for k in ("dt", "regions", "sustained", "kern", "kern_steps", "fused"))
 
     def frame_stats():

@@ -3,11 +3,10 @@
   * the header-only glm the rasterizer vendors (DGR/third_party/glm), through oracle/glm_probe.cpp: a probe of
     glm's mat3 operator* / transpose, the operand order every bit-exact key of the rasterizer depends on.
 
-Runs ONLY in the authoring container (needs /root/reference).  Output goes OUTSIDE the repository tree
-($HGS_REF_OUT, default /tmp/hgs_ref): nothing compiled from the reference is ever part of the snapshot that
-travels to the GPU box -- only the numeric fixtures generated with it (tests/golden/*.npz) and the timing
-recorded in BASELINE.md do.  No reference source is copied: the .pyx is cythonized where it lies, the generated
-C lands in a temp dir.
+Runs ONLY in the authoring container (needs /root/reference).  Output goes to oracle/_ref/ ($HGS_REF_OUT overrides),
+git-ignored: nothing compiled from the reference is part of the repository, and no test, smoke() or bench.py reads
+it -- only the numeric fixtures generated with it (tests/golden/*.npz) and the timing recorded in BASELINE.md are.
+No reference source is copied: the .pyx is cythonized where it lies, the generated C lands in a temp dir.
 
 The CUDA rasterizer / simple-knn sources are NOT buildable here (need nvcc, cuda_runtime,
 cooperative_groups, CUB, thrust) and no stand-ins are written for them -- see DESIGN.md.
@@ -21,9 +20,8 @@ import sysconfig
 import tempfile
 
 REF = "/root/reference/c_utils/c_utils.pyx"
-OUT = os.environ.get("HGS_REF_OUT", "/tmp/hgs_ref")
 _HERE = os.path.dirname(os.path.abspath(__file__))
-assert not os.path.abspath(OUT).startswith(os.path.dirname(_HERE) + os.sep), "HGS_REF_OUT must lie outside the repository"
+OUT = os.environ.get("HGS_REF_OUT", os.path.join(_HERE, "_ref"))
 
 
 def build():

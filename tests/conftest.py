@@ -3,6 +3,12 @@ import sys
 
 import pytest
 
+# The golden fixtures pin the reference's torch statements bit for bit on the CPU.  MKL's vector math (torch.exp, log, ...)
+# picks its code path by CPU vendor and ISA, torch's own kernels by ISA: both are fixed here, before any torch operation,
+# to what tests/golden/_ref_harness.py fixes for the generators, so that the pins hold on every x86-64 test host.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+os.environ["ATEN_CPU_CAPABILITY"] = "avx2"
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 PKG = os.path.join(ROOT, "hair-gs_amd")
 for p in (ROOT, PKG):

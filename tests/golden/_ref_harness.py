@@ -4,10 +4,18 @@ The reference's modules import, at module level, third-party packages this image
 diff_gaussian_rasterization, cv2, pyrr, pyvista, pyvistaqt, dreifus, wandb, tensorboard).  `install_placeholders()` makes
 those names importable as EMPTY modules whose every attribute raises when called: the generators only run reference
 methods that never reach them (a call aborts the generation).  Nothing of the reference is edited, wrapped or copied.
+
+Importing this module fixes the CPU arithmetic the fixtures are computed with to the one tests/conftest.py fixes for the
+tests (the two must stay the same): MKL's vector math (torch.exp, log, ...) picks its code path by CPU vendor and ISA unless
+MKL_CBWR pins it, and torch's own kernels by ISA unless ATEN_CPU_CAPABILITY does.  Both are read at first use, so the
+generators import this module before any torch operation.
 """
 import os
 import sys
 import types
+
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+os.environ["ATEN_CPU_CAPABILITY"] = "avx2"
 
 REF = "/root/reference"
 ABSENT = ("pytorch3d", "pytorch3d.ops", "pytorch3d.transforms", "plyfile", "simple_knn", "simple_knn._C",

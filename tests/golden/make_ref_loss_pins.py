@@ -1,11 +1,12 @@
 """Generates tests/golden/ref_loss_pins.npz by RUNNING the reference's own loss code (loss/losses.py) and the reference
-model's own getters on the CPU of the authoring container.  Only numeric inputs and outputs are stored.
+model's own getters on the CPU of the authoring container.  Only numeric inputs and outputs are stored -- the L1 + SSIM
+images as the sha256 of their bytes: ssim_inputs() draws them again from the seeded stream.
 
 Executed, unedited (values and, through autograd, gradients):
   * l1_loss, ssim                                   loss/losses.py:16-17, 43-84     (F.conv2d on the CPU)
   * angle_smoothness_loss(gaussians, threshold)     :175-221    on reference HairGaussianModels (device="cpu") built from the
                                                                 states of ref_topology_pins.npz; c_utils = the reference's
-                                                                own .pyx, built by oracle/build_ref.py outside the repository
+                                                                own .pyx, built by oracle/build_ref.py into the git-ignored oracle/_ref/
   * orientation_loss_rast, mask_loss_rast           :224-316    see (2) below
   * loss_function                                   :319-355    the five terms and the weighted total
   * HairGaussianModel.get_scaling / get_xyz / get_orientation / get_opacity / get_mask   scene/hair_gaussian_model.py:135-201
@@ -23,6 +24,7 @@ What stands in for things this image lacks (all of it stated here, none of it in
   (4) cameras are plain attribute holders with the fields the loss functions read.
 """
 import argparse
+import hashlib
 import os
 import sys
 import types
@@ -33,6 +35,25 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, "..", ".."))
 OUT = os.path.join(HERE, "ref_loss_pins.npz")
 SMOOTH_SEEDS = [0, 1, 2, 3, 100, 101]
+INPUT_SEED = 20261003                                  # the one random stream every input of the fixture is drawn from
+SSIM_CASES = [(61, 97), (64, 100), (33, 17), (96, 128), (40, 40)]
+
+
+def ssim_inputs(rng, ci, H, W):
+    """(image, target) of L1 + SSIM case `ci`: the first draws of the stream, case after case.  They are not stored (the
+    fixture holds their sha256, `ssim<ci>_inputs_sha256`): tests/test_ref_loss_pins.py draws them again with this function."""
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    a = f32(rng.uniform(0, 1, (3, H, W)))
+    b = f32(np.clip(a + rng.normal(0, 0.1, (3, H, W)), 0, 1))
+    if ci >= 3:                                        # black background outside a box, like a hair render and its target
+        keep = np.zeros((H, W), bool)
+        keep[H // 4:H // 4 + H // 3, W // 5:W // 5 + W // 2] = True
+        a, b = a * keep, b * np.roll(keep, 2, axis=1)
+    return a, b
+
+
+def inputs_sha256(a, b):
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes() + np.ascontiguousarray(b).tobytes()).digest(), np.uint8)
 
 
 def main():
@@ -59,20 +80,14 @@ def main():
     from arguments import OptimizationParams
     from scene.hair_gaussian_model import HairGaussianModel
     opt = OptimizationParams(argparse.ArgumentParser())
-    rng = np.random.default_rng(20261003)
+    rng = np.random.default_rng(INPUT_SEED)
     out = {}
     f32 = lambda a: np.asarray(a, dtype=np.float32)
 
     # ---- L1 + SSIM ---------------------------------------------------------------------------------------------------------
-    cases = [(61, 97), (64, 100), (33, 17), (96, 128), (40, 40)]
-    out["meta_ssim_cases"] = np.array(cases)
-    for ci, (H, W) in enumerate(cases):
-        a = f32(rng.uniform(0, 1, (3, H, W)))
-        b = f32(np.clip(a + rng.normal(0, 0.1, (3, H, W)), 0, 1))
-        if ci >= 3:                                        # black background outside a box, like a hair render and its target
-            keep = np.zeros((H, W), bool)
-            keep[H // 4:H // 4 + H // 3, W // 5:W // 5 + W // 2] = True
-            a, b = a * keep, b * np.roll(keep, 2, axis=1)
+    out["meta_ssim_cases"] = np.array(SSIM_CASES)
+    for ci, (H, W) in enumerate(SSIM_CASES):
+        a, b = ssim_inputs(rng, ci, H, W)
         x = torch.from_numpy(a).requires_grad_(True)
         y = torch.from_numpy(b)
         s = RL.ssim(x, y)
@@ -80,7 +95,7 @@ def main():
         l = RL.l1_loss(x, y)
         gl, = torch.autograd.grad(l, x)
         k = f"ssim{ci}_"
-        out[k + "img"], out[k + "gt"] = a, b
+        out[k + "inputs_sha256"] = inputs_sha256(a, b)
         out[k + "ssim"], out[k + "l1"] = np.float64(s.item()), np.float64(l.item())
         out[k + "d_ssim"], out[k + "d_l1"] = gs.numpy(), gl.numpy()
 

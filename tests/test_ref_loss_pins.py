@@ -8,6 +8,8 @@ scene/hair_gaussian_model.py executed unedited, values and autograd gradients).
     vectors directly, through the C ABI.
 Tolerances are written where they apply; fp32 throughout.
 """
+import functools
+import importlib.util
 import os
 import types
 
@@ -23,6 +25,21 @@ TOPO = np.load(os.path.join(_HERE, "golden", "ref_topology_pins.npz"))
 SSIM_CASES = [tuple(int(v) for v in r) for r in PINS["meta_ssim_cases"]]
 MODEL_SEEDS = [int(s) for s in PINS["meta_smooth_seeds"]]
 HEAD_CASES = [tuple(int(v) for v in r) for r in PINS["meta_head_cases"]]
+_spec = importlib.util.spec_from_file_location("make_ref_loss_pins", os.path.join(_HERE, "golden", "make_ref_loss_pins.py"))
+GEN = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(GEN)          # (only its seeded input builder is used: ssim_inputs())
+
+
+@functools.lru_cache(maxsize=None)
+def _ssim_inputs(ci):
+    """(image, target) of L1 + SSIM case `ci`, drawn again from the fixture's random stream (the fixture holds their sha256, not
+    the images): bit for bit what the reference was given."""
+    assert [tuple(c) for c in GEN.SSIM_CASES] == SSIM_CASES
+    rng = np.random.default_rng(GEN.INPUT_SEED)
+    for cj, (H, W) in enumerate(SSIM_CASES[:ci + 1]):
+        a, b = GEN.ssim_inputs(rng, cj, H, W)
+    assert np.array_equal(GEN.inputs_sha256(a, b), PINS[f"ssim{ci}_inputs_sha256"]), ci
+    return a, b
 
 
 def _t(a, device):
@@ -65,8 +82,9 @@ def _close(got, want, rel, what, floor=0.0, where=None):
 def test_torch_ssim_and_l1_reproduce_the_reference_run(ci):
     from loss import losses as Ls
     k = f"ssim{ci}_"
-    x = _t(PINS[k + "img"], "cpu").requires_grad_(True)
-    y = _t(PINS[k + "gt"], "cpu")
+    img, gt = _ssim_inputs(ci)
+    x = _t(img, "cpu").requires_grad_(True)
+    y = _t(gt, "cpu")
     s = Ls.ssim(x, y)
     gs, = torch.autograd.grad(s, x)
     l = Ls.l1_loss(x, y)
@@ -175,8 +193,9 @@ def test_hip_ssim_l1_against_the_reference_run(ci):
     window quotients, hardware reciprocals), L1 to 1e-6 relative, gradients to 2e-4 of their largest element."""
     from hgs_runtime.fused import ssim_l1
     k = f"ssim{ci}_"
-    x = _t(PINS[k + "img"], "cuda").requires_grad_(True)
-    y = _t(PINS[k + "gt"], "cuda")
+    img, gt = _ssim_inputs(ci)
+    x = _t(img, "cuda").requires_grad_(True)
+    y = _t(gt, "cuda")
     s, l = ssim_l1(x, y)
     gs, = torch.autograd.grad(s, x, retain_graph=True)
     gl, = torch.autograd.grad(l, x)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""BASELINE.md B2, reference side: the reference's own c_utils.pyx (built by oracle/build_ref.py OUTSIDE the repository)
+"""BASELINE.md B2, reference side: the reference's own c_utils.pyx (built by oracle/build_ref.py into the git-ignored oracle/_ref/)
 against this package's native module on the same cores.  Runs in the authoring container only (needs /root/reference);
 its output is recorded in BASELINE.md -- nothing compiled from the reference travels to the GPU box."""
 import json, os, sys, time
