@@ -206,7 +206,7 @@ struct BlendItem { int tile; uint32_t seg, nseg, s, e, w; uint2 range; bool spli
 // first, a tile's segments consecutive, then the other tiles in descending order of list length).  The work item and the
 // counters are independent loads, the tile's range the only dependent one: two memory round trips before the walk starts.
 __device__ __forceinline__ bool blend_item(const HgsImage& im, uint32_t Rcap, BlendItem& it) {
-  const uint4 st = *(const uint4*)(im.status + HGS_ST_SORT_ITEMS);   // [4..7]: -, split items, segment length, work items
+  const uint4 st = *(const uint4*)(im.status + HGS_ST_SORT_ITEMS);   // [4..7]: -, split items, segment length, work items (status: a 256-B boundary, hgs_image_zero_layout)
   const uint32_t item = im.tile_order[blockIdx.x];
   if (blockIdx.x >= st.w || item == HGS_ITEM_NONE) return false;
   it.w = blockIdx.x;

@@ -143,28 +143,52 @@ static inline size_t hgs_geom_carve(char* base, size_t P, HgsGeom& g, size_t* of
 // spread over all of them.
 static inline size_t hgs_tile_slots(size_t T) { size_t n = 64; while (n < T) n <<= 1; return n; }
 #define HGS_TILE_SLOT(t, mask) ((uint32_t)((uint32_t)(t) * 0x9E3779B1u) & (uint32_t)(mask))
-static inline size_t hgs_tile_delta_words(size_t T) { return (T + 2) & ~(size_t)1; }   // T + 1 entries, even (tile_prog stays 8-byte aligned)
-static inline size_t hgs_image_zero_words(size_t T) { return 2 * hgs_tile_slots(T) + hgs_tile_delta_words(T) + 2 * T + HGS_STATUS_WORDS + 4 * T; }
+static inline size_t hgs_tile_delta_words(size_t T) { return (T + 2) & ~(size_t)1; }   // T + 1 entries, even
+static inline size_t hgs_line_words(size_t w) { return (w + HGS_ALIGN / 4 - 1) & ~(size_t)(HGS_ALIGN / 4 - 1); }   // words -> whole 256-B lines
+// Word offsets inside the zero range, which starts at tile_count on a 256-byte boundary.  tile_count, tile_delta and
+// tile_cursor are packed (tile_delta's T + 1 marks end where the cursors start -- an even number of words, so the cursors sit
+// 8 bytes off a 16-byte boundary whenever T % 4 < 2; only 32-bit atomics at scattered slots touch them); every field behind
+// them starts on a 256-byte boundary of its own: tile_maxc is read as uint4 by the loss head's list builder (HgsHeadParams.
+// tile_used), status[4..7] as one 16-byte load by every blend workgroup, tile_prog / tile_sortprog take 64-bit atomics.
+// (Round 6 inserted tile_delta with everything behind it packed: at 1920x1080 that put tile_maxc and status 8 bytes off
+// a 16-byte boundary, and the loss head dropped the misaligned hint without a word.)
+struct HgsImageZero { size_t delta, cursor, maxc, done, status, prog, sortprog, words; };
+static inline HgsImageZero hgs_image_zero_layout(size_t T) {
+  const size_t Tp = hgs_tile_slots(T);
+  HgsImageZero z;
+  z.delta = Tp;
+  z.cursor = z.delta + hgs_tile_delta_words(T);
+  z.maxc = hgs_line_words(z.cursor + Tp);
+  z.done = hgs_line_words(z.maxc + T);
+  z.status = hgs_line_words(z.done + T);
+  z.prog = hgs_line_words(z.status + HGS_STATUS_WORDS);
+  z.sortprog = hgs_line_words(z.prog + 2 * T);
+  z.words = hgs_line_words(z.sortprog + 2 * T);
+  return z;
+}
+static inline size_t hgs_image_zero_words(size_t T) { return hgs_image_zero_layout(T).words; }
 static inline size_t hgs_image_carve(char* base, size_t W, size_t H, HgsImage& im, size_t* offs) {
   char* cur = base;
   size_t N = W * H, T = ((W + HGS_TILE - 1) / HGS_TILE) * ((H + HGS_TILE - 1) / HGS_TILE);
   hgs_carve(cur, im.final_T, N);            if (offs) offs[HGS_IMG_FINAL_T] = (char*)im.final_T - base;
   hgs_carve(cur, im.n_contrib, N);          if (offs) offs[HGS_IMG_N_CONTRIB] = (char*)im.n_contrib - base;
   hgs_carve(cur, im.ranges, T);             if (offs) offs[HGS_IMG_RANGES] = (char*)im.ranges - base;
-  // the next seven are zeroed together by one fill in hgs_forward_preprocess (HGS_IMG_ZERO_WORDS)
+  // the next seven are zeroed together by one fill in hgs_forward_preprocess (hgs_image_zero_words; hgs_image_zero_layout)
   const size_t Tp = hgs_tile_slots(T);
+  const HgsImageZero z = hgs_image_zero_layout(T);
   im.tile_mask = (uint32_t)(Tp - 1);
-  hgs_carve(cur, im.tile_count, T);         if (offs) offs[HGS_IMG_TILE_COUNT] = (char*)im.tile_count - base;   // (Tp slots: below)
+  hgs_carve(cur, im.tile_count, T);         if (offs) offs[HGS_IMG_TILE_COUNT] = (char*)im.tile_count - base;   // (Tp slots)
+  uint32_t* const zr = im.tile_count;
   // (tile_delta sits between the counters and the cursors: like tile_count it is left at zero by its last reader, not by the
   // prologue rider, whose range starts at tile_cursor -- the rider runs beside the workgroups that add to both)
-  im.tile_delta = (int32_t*)(im.tile_count + Tp);
-  im.tile_cursor = im.tile_count + Tp + hgs_tile_delta_words(T);  if (offs) offs[HGS_IMG_TILE_CURSOR] = (char*)im.tile_cursor - base;
-  im.tile_maxc = im.tile_cursor + Tp;       if (offs) offs[HGS_IMG_TILE_MAXC] = (char*)im.tile_maxc - base;
-  im.tile_done = im.tile_maxc + T;
-  im.status = im.tile_done + T;             if (offs) offs[HGS_IMG_STATUS] = (char*)im.status - base;
-  im.tile_prog = (unsigned long long*)(im.status + HGS_STATUS_WORDS);   // 8-byte aligned: an even number of words past a 256-B boundary
-  im.tile_sortprog = im.tile_prog + T;
-  cur += hgs_image_zero_words(T) * sizeof(uint32_t);
+  im.tile_delta = (int32_t*)(zr + z.delta);
+  im.tile_cursor = zr + z.cursor;           if (offs) offs[HGS_IMG_TILE_CURSOR] = (char*)im.tile_cursor - base;
+  im.tile_maxc = zr + z.maxc;               if (offs) offs[HGS_IMG_TILE_MAXC] = (char*)im.tile_maxc - base;
+  im.tile_done = zr + z.done;
+  im.status = zr + z.status;                if (offs) offs[HGS_IMG_STATUS] = (char*)im.status - base;
+  im.tile_prog = (unsigned long long*)(zr + z.prog);
+  im.tile_sortprog = (unsigned long long*)(zr + z.sortprog);
+  cur = (char*)(zr + z.words);
   hgs_carve(cur, im.sort_items, T);
   // the blend kernels' work list (sort_tiles_kernel): workgroup -> tile | segment << 24; segments of split lists first,
   // then the other tiles in descending order of list length.  T + HGS_SPLIT_CAPACITY(T) entries.

@@ -815,9 +815,10 @@ __device__ __forceinline__ void head_part1(const HeadReduce& h, const float* __r
 #ifndef HGS_PIX_TRACE
 #define HGS_PIX_TRACE 0   // development aid: timestamps of the side workgroups behind the block lists (tools/dev/pix_trace.py)
 #endif
-#define HEAD_MAX_TILES 32768     // tiles of a frame the list builder keeps the use bits of (4K: 32400); more: the hint is ignored
+#define HEAD_MAX_TILES 45056     // tiles of a frame the list builder keeps the use bits of: any frame of at most HEAD_MAX_FLAGGED SSIM blocks
 #define HEAD_MAX_FLAGGED 32768   // SSIM blocks of a frame the backward's block lists are built for (4K RGB: 24480); without the lists (and the zero-block flags that come with them) the SSIM pair takes 90 instead of 77 us at north_star
 static_assert(HEAD_MAX_FLAGGED % (32 * 256) == 0, "whole 32-block words per thread of the list builder");
+static_assert(HEAD_MAX_TILES % 32 == 0 && HEAD_MAX_TILES >= 4 * (HEAD_MAX_FLAGGED / 3), "2 x 2 tiles per block of 3 channels");
 // Block lists of the SSIM backward, built by ONE workgroup of pix_fwd_kernel (the SSIM forward before that launch flagged
 // the blocks whose halo tile is exactly zero in both images): lists = [n_work, n_skip, -, -][ids of the blocks with a
 // non-zero gradient, logical order][the other ids].  A block has work unless its whole 3x3 neighbourhood is flagged: then
@@ -861,8 +862,7 @@ __device__ __forceinline__ void build_block_lists(const SsimGrid& gd, const unsi
   const int total = gd.total, nwords = (total + 31) >> 5;
   const unsigned* zf = (const unsigned*)zero_flags;   // (4-byte aligned: the flags start on a float of the scratch)
   const int n_tiles = tiles_x * tiles_y;
-  if (tile_used && (n_tiles > HEAD_MAX_TILES || ((size_t)tile_used & 15))) tile_used = nullptr;
-  const uint4* tu4 = (const uint4*)tile_used;
+  const uint4* tu4 = (const uint4*)tile_used;          // (16-byte aligned, at most HEAD_MAX_TILES tiles: hgs_loss_head_forward checked)
   const int n4 = (n_tiles + 3) >> 2;
   uint4 tv[8];
   if (tile_used) {
@@ -1262,6 +1262,15 @@ int hgs_loss_head_forward(void* stream, const HgsHeadParams* p, const float* ima
   if (p->tile_used && (p->tiles_x != (W + HGS_TILE - 1) / HGS_TILE || p->tiles_y != (H + HGS_TILE - 1) / HGS_TILE)) {
     hgs_set_error("hgs_loss_head_forward: tile_used given with tiles_x / tiles_y = %d x %d, the %d x %d frame has %d x %d tiles", p->tiles_x,
                   p->tiles_y, W, H, (W + HGS_TILE - 1) / HGS_TILE, (H + HGS_TILE - 1) / HGS_TILE);
+    return 1;
+  }
+  // the list builder reads the hint as uint4 into a bitmap of HEAD_MAX_TILES tiles (a misaligned hint is an error, never
+  // dropped: round 6's image layout put the contributor counts 8 bytes off a 16-byte boundary, and the SSIM backward went
+  // back to filtering every block without a word)
+  if (p->tile_used && (((size_t)p->tile_used & 15) ||
+                       (head_nb_ssim(p) <= HEAD_MAX_FLAGGED && (size_t)p->tiles_x * p->tiles_y > HEAD_MAX_TILES))) {
+    hgs_set_error("hgs_loss_head_forward: tile_used %p covers %d x %d tiles, it must be 16-byte aligned and cover at most %d", (const void*)p->tile_used,
+                  p->tiles_x, p->tiles_y, HEAD_MAX_TILES);
     return 1;
   }
   const int nbs = head_nb_ssim(p), nbp = head_nb_pix(p), nbm = head_nb_smooth(p);

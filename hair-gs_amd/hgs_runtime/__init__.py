@@ -176,7 +176,7 @@ HEAD_OUT = ["total", "l1", "dssim", "mask", "orientation", "smooth", "ori_count"
             "g_ori", "g_smooth", "total_fwd"]
 HEAD_NOUT = 16
 FUSED_PREPROCESS_MAX_TILES = 8192   # include/hgs.h HGS_FUSED_PREPROCESS_MAX_TILES
-ABI_VERSION = 6   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
+ABI_VERSION = 7   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
 
 
 def build(verbose=False):

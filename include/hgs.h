@@ -44,9 +44,11 @@ extern "C" {
 
 /* bumped with every incompatible change of a struct, a signature or a buffer layout (round 1: 1, round 2: 2, round 3: 3, then 4 with the one-launch parameters + preprocess entry points;
  * 5, round 5: hgs_backward_multi_params / hgs_hair_endpoint_gather, HgsPrologue.adam_prep and the in-lane Adam update, and the contract that HgsHeadParams.tile_used also limits
- * what hgs_loss_head_forward writes of d_extra_unit -- a caller of version 4 that read those planes everywhere must not);
+ * what hgs_loss_head_forward writes of d_extra_unit -- a caller of version 4 that read those planes everywhere must not;
+ * 6, round 6: tile_delta in the image buffer; 7: every image-buffer field behind tile_cursor starts on a 256-byte boundary, and a
+ * misaligned HgsHeadParams.tile_used is an error of hgs_loss_head_forward);
  * the Python binding refuses a library whose version or struct sizes differ from its own */
-#define HGS_ABI_VERSION 6
+#define HGS_ABI_VERSION 7
 #define HGS_TILE 16 /* cuda_rasterizer/config.h:16-17 */
 
 int hgs_abi_version(void);
@@ -457,7 +459,7 @@ typedef struct HgsHeadParams {
    * HGS_IMG_TILE_MAXC) of the forward pass that produced `image`: it touches dL/dpixel only where a pixel blended an entry.
    * With the hint, hgs_loss_head_backward leaves d_image UNWRITTEN on 32 x 32 blocks none of whose tiles is read (it
    * neither filters nor zero-fills them), and hgs_loss_head_forward leaves d_extra_unit UNWRITTEN on the tiles that are
-   * not read. */
+   * not read.  The hint must be 16-byte aligned (HGS_IMG_TILE_MAXC is): hgs_loss_head_forward fails otherwise. */
   const unsigned int* tile_used; int tiles_x, tiles_y;
 } HgsHeadParams;
 enum { HGS_HEAD_TOTAL = 0, HGS_HEAD_L1, HGS_HEAD_DSSIM, HGS_HEAD_MASK, HGS_HEAD_ORIENTATION, HGS_HEAD_SMOOTH,
