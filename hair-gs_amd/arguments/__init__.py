@@ -84,7 +84,8 @@ class GeneralParams(ParamGroup):
     NAME = "General Parameters"
     FIELDS = (("quiet", False, False), ("logger", "tensorboard", False), ("ip", "127.0.0.1", False), ("port", 6009, False),
               ("vis2d", False, False), ("update_vis2d_frequency", 30000, False), ("vis3d", False, False),
-              ("save_frequency", 5000, False), ("eval_frequency", 30000, False))
+              ("save_frequency", 5000, False), ("eval_frequency", 30000, False),
+              ("eval_device", "cpu", False))   # strand metrics of train.py evaluate(): cpu, or a GPU device (loss/metrics.py)
 
 
 def get_combined_args(parser: ArgumentParser):

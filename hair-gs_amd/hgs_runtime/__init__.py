@@ -84,6 +84,9 @@ SIGNATURES = {
     "hgs_nearest_distance_f64": (ci, [vp, ci, ci, vp, vp, vp]),
     "hgs_strand_walk_ends": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp]),
     "hgs_strand_walk_fill": (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp]),
+    "hgs_oriented_match_scratch_bytes": (sz, [ci]),
+    "hgs_oriented_match": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, sz]),
+    "hgs_strand_votes": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]),
     "hgs_set_tile_cull": (ci, [ci]),
     "hgs_set_segment_policy": (ci, [ci, ci, ci]),
     "hgs_set_row_reduce": (ci, [ci]),

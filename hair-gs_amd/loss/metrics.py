@@ -1,8 +1,13 @@
 """Strand-reconstruction metrics (counterpart of the reference's loss/metrics.py:12-173): precision / recall / F1 of
-oriented points under (distance, angle) thresholds and strand consistency.  CPU code (scipy cKDTree), a reported
-baseline of the path, not an optimisation target.  Instead of the reference's Python loop over
-every point, the radius-query result is flattened to CSR arrays and reduced with numpy; the threshold pairs run on a
-thread pool (cKDTree releases the GIL) instead of 8 forked processes with a Manager dict."""
+oriented points under (distance, angle) thresholds and strand consistency.  Two backends behind compute_metrics(device=):
+  * CPU (default, scipy cKDTree).  Instead of the reference's Python loop over every point, the radius-query result is
+    flattened to CSR arrays and reduced with numpy; the threshold pairs run on a thread pool (cKDTree releases the GIL)
+    instead of 8 forked processes with a Manager dict.
+  * GPU (csrc/hgs_metrics.hip): one pass per direction tests every threshold pair (per-point bitmasks), and one workgroup
+    per strand counts the consistency votes.  Both backends hand integer counts to the same host arithmetic (_ratio,
+    _consistency, _assemble), so the dicts are equal bit for bit wherever the per-point matches agree.  (The GPU path
+    takes every dot product in float64; the CPU path's einsum does too unless BOTH sides' directions are float32.)"""
+import warnings
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 from typing import Optional
@@ -45,7 +50,7 @@ def pct_matched_points(p1, p2, dist_th, angle_th, bidirectional=False, compute_s
     rows, cols = _csr_matches(p1, p2, dist_th, cos_th, bidirectional)
     matched = np.zeros(n, bool)
     matched[rows] = True
-    ratio = matched.sum() / n
+    ratio = _ratio(matched.sum(), n)
     consistency = None
     if compute_strand_consistency:
         s1 = p1.points_id_to_strand_id
@@ -53,25 +58,57 @@ def pct_matched_points(p1, p2, dist_th, angle_th, bidirectional=False, compute_s
         strands, n_pts = np.unique(s1, return_counts=True)
         # each p1 point votes once for every distinct p2 strand it matched
         votes = np.unique(np.stack([rows, s2[cols]], 1), axis=0) if rows.size else np.zeros((0, 2), np.int64)
-        total = 0.0
+        best = np.zeros(len(strands), np.int64)
         if votes.shape[0]:
             key = np.stack([s1[votes[:, 0]], votes[:, 1]], 1)          # (p1 strand, p2 strand)
             uk, cnt = np.unique(key, axis=0, return_counts=True)
-            best = {}
-            for (a, _), c in zip(uk, cnt):
-                best[a] = max(best.get(a, 0), c)
-            size = dict(zip(strands.tolist(), n_pts.tolist()))
-            total = sum(c / size[a] for a, c in best.items())
-        consistency = total / len(strands)
+            np.maximum.at(best, np.searchsorted(strands, uk[:, 0]), cnt)
+        consistency = _consistency(best, n_pts)
     return ratio, consistency
 
 
+# ---- the host arithmetic both backends share: integer counts -> the ratios the reference reports ----
+def _ratio(matched, n):
+    """matched points (an integer) / n: a numpy float64 (nan for n == 0, as numpy divides)."""
+    return np.int64(matched) / n
+
+
+def _consistency(best, sizes):
+    """Strand consistency from best[s] = the most points of strand s that one strand of the other side matched, and sizes[s] =
+    its point count, strands in ascending id order: sum(best / size) over the strands with a vote, in that order, divided by the
+    strand count (ZeroDivisionError without strands, like the reference)."""
+    best, sizes = np.asarray(best, np.int64), np.asarray(sizes, np.int64)
+    voted = best > 0
+    total = sum(c / s for c, s in zip(best[voted], sizes[voted].tolist())) if voted.any() else 0.0
+    return total / len(sizes)
+
+
+def _assemble(out, n_pairs, bidirectional):
+    """{metric: {pair index: value}} -> the reference's {metric[(b)]: array over thresholds}, with F1 from precision and recall."""
+    if "f1" in out and "precision" in out and "recall" in out:
+        for i in range(n_pairs):
+            p, r = out["precision"].get(i), out["recall"].get(i)
+            if p is not None and r is not None:
+                out["f1"][i] = 2 * p * r / (p + r) if p + r > 0 else 0
+    suffix = "(b)" if bidirectional else ""
+    return {k + suffix: np.array([v[i] for i in range(n_pairs) if i in v]) for k, v in out.items()}
+
+
 def compute_metrics(pred, gt, dist_ths=(2e-3, 3e-3, 4e-3, 4e-3), angle_ths=(20, 30, 40, 90),
-                    metrics=("precision", "recall", "f1", "strand_consistency"), bidirectional=False, processes=None):
-    """Returns ({metric[(b)]: array over thresholds}, [threshold labels]) like the reference (:88-173)."""
+                    metrics=("precision", "recall", "f1", "strand_consistency"), bidirectional=False, processes=None,
+                    device=None, vote_capacity=None):
+    """Returns ({metric[(b)]: array over thresholds}, [threshold labels]) like the reference (:88-173).
+
+    device None (or a CPU device): the CPU path below.  A CUDA device: the HIP kernels of csrc/hgs_metrics.hip; the same dict,
+    bit for bit, wherever the per-point matches agree (see oriented_match).  There is no fallback: without a GPU it raises
+    HgsError.  vote_capacity: LDS entries of the strand-vote tables (GPU path; a power of two, default VOTE_CAPACITY)."""
     consistency = ("strand_consistency" in metrics and pred.points_id_to_strand_id is not None
                    and gt.points_id_to_strand_id is not None)
     labels = [f"{d}m&{a}°" for d, a in zip(dist_ths, angle_ths)]
+    if device is not None and str(device) != "cpu":
+        out = _metrics_gpu(pred, gt, dist_ths, angle_ths, metrics, bidirectional, consistency, device,
+                           VOTE_CAPACITY if vote_capacity is None else vote_capacity)
+        return _assemble(out, len(labels), bidirectional), labels
     jobs = []
     if "precision" in metrics:
         jobs += [("precision", i, pred, gt, d, a, False) for i, (d, a) in enumerate(zip(dist_ths, angle_ths))]
@@ -86,13 +123,145 @@ def compute_metrics(pred, gt, dist_ths=(2e-3, 3e-3, 4e-3, 4e-3), angle_ths=(20, 
             out[name][i] = ratio
             if cons is not None:
                 out["strand_consistency"][i] = cons
-    if "f1" in out and "precision" in out and "recall" in out:
-        for i in range(len(labels)):
-            p, r = out["precision"].get(i), out["recall"].get(i)
-            if p is not None and r is not None:
-                out["f1"][i] = 2 * p * r / (p + r) if p + r > 0 else 0
-    suffix = "(b)" if bidirectional else ""
-    return ({k + suffix: np.array([v[i] for i in range(len(labels)) if i in v]) for k, v in out.items()}, labels)
+    return _assemble(out, len(labels), bidirectional), labels
+
+
+# ---- GPU path (csrc/hgs_metrics.hip through include/hgs.h hgs_oriented_match / hgs_strand_votes) ----
+MAX_PAIRS = 32            # threshold pairs per kernel pass (bits of the per-point mask)
+VOTE_CAPACITY = 2048      # largest LDS table of hgs_strand_votes
+
+
+def _gpu_device(device):
+    import torch
+    import hgs_runtime as rt
+    dev = torch.device(device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise rt.HgsError(f"strand metrics on device {device!r}: libhgs.so only runs on the GPU, there is no CPU fallback "
+                          "(device=None selects the CPU path)")
+    return dev
+
+
+def _box(points):
+    """Per-axis min and max of the finite coordinates (a NaN point never matches and may lie anywhere)."""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)       # (an axis without a finite value: all-NaN slice)
+        finite = np.where(np.isfinite(points), points, np.nan)
+        lo, hi = np.nanmin(finite, 0), np.nanmax(finite, 0)
+    return np.ascontiguousarray(np.nan_to_num(np.concatenate([lo, hi]), nan=0.0), np.float64)
+
+
+class _GpuSide:
+    """One point set uploaded as float64 (float32 input widens exactly), optionally reordered."""
+
+    def __init__(self, data, dev, order=None):
+        import torch
+        p, d = np.asarray(data.points, np.float64), np.asarray(data.directions, np.float64)
+        if order is not None:
+            p, d = p[order], d[order]
+        self.n = p.shape[0]
+        self.host_points, self.host_dirs = p, d
+        self.points = torch.from_numpy(np.ascontiguousarray(p.reshape(-1, 3))).to(dev)
+        self.dirs = torch.from_numpy(np.ascontiguousarray(d.reshape(-1, 3))).to(dev)
+        self.box = _box(p.reshape(-1, 3)) if self.n else np.zeros(6)
+
+
+def _match_pass(A, B, pairs, bidirectional, dev):
+    """hgs_oriented_match of A against B for <= MAX_PAIRS (r, cos) pairs: (uint32 mask tensor [nA], scratch, thresholds)."""
+    import torch
+    import hgs_runtime as rt
+    L = rt.lib()
+    thr = np.ascontiguousarray(np.asarray(pairs, np.float64).reshape(-1, 2))
+    mask = torch.empty(A.n, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(L.hgs_oriented_match_scratch_bytes(B.n)), dtype=torch.uint8, device=dev)
+    rt.check(L.hgs_oriented_match(rt.current_stream(), A.n, B.n, len(pairs), rt.ptr(A.points), rt.ptr(A.dirs), rt.ptr(B.points),
+                                  rt.ptr(B.dirs), thr.ctypes.data, int(bool(bidirectional)), B.box.ctypes.data, rt.ptr(mask),
+                                  rt.ptr(scratch), scratch.numel()))
+    return mask, scratch, thr
+
+
+def oriented_match(a, b, dist_ths, cos_ths, bidirectional=False, device="cuda"):
+    """Per point of `a` (HairEvalData): a uint32 bitmask, bit k set iff some point of `b` lies within dist_ths[k] -- decided as
+    d2 = (dx*dx + dy*dy) + dz*dz <= r*r in float64, the form cKDTree.query_ball_point decides by -- with direction
+    dot >= cos_ths[k] (|dot| if bidirectional).  At most MAX_PAIRS pairs.  What the metrics of the GPU path count."""
+    import torch
+    dev = _gpu_device(device)
+    pairs = [(float(d), float(c)) for d, c in zip(dist_ths, cos_ths)]
+    if not 1 <= len(pairs) <= MAX_PAIRS:
+        raise ValueError(f"oriented_match: 1 .. {MAX_PAIRS} threshold pairs, got {len(pairs)}")
+    with torch.cuda.device(dev):
+        A, B = _GpuSide(a, dev), _GpuSide(b, dev)
+        if A.n == 0:
+            return np.zeros(0, np.uint32)
+        mask, _, _ = _match_pass(A, B, pairs, bidirectional, dev)
+        return mask.cpu().numpy().view(np.uint32)
+
+
+def _counts(mask, K):
+    m = mask.cpu().numpy().view(np.uint32)
+    return [np.count_nonzero(m & np.uint32(1 << k)) for k in range(K)]
+
+
+def _host_best(A, lo, hi, B, b_strand, pair, bidirectional):
+    """The vote count of one strand (A's points lo..hi) under one pair, on the host: for strands the LDS tables cannot hold."""
+    sub = HairEvalData(A.host_points[lo:hi], A.host_dirs[lo:hi])
+    rows, cols = _csr_matches(sub, HairEvalData(B.host_points, B.host_dirs), pair[0], pair[1], bidirectional)
+    if rows.size == 0:
+        return 0
+    votes = np.unique(np.stack([rows, b_strand[cols].astype(np.int64)], 1), axis=0)
+    return int(np.unique(votes[:, 1], return_counts=True)[1].max())
+
+
+def _metrics_gpu(pred, gt, dist_ths, angle_ths, metrics, bidirectional, consistency, device, vote_capacity):
+    """{metric: {pair index: value}} of compute_metrics on the GPU: one pass per direction for up to MAX_PAIRS pairs."""
+    import torch
+    import hgs_runtime as rt
+    dev = _gpu_device(device)
+    pairs = [(float(d), float(np.cos(np.deg2rad(a)))) for d, a in zip(dist_ths, angle_ths)]   # (the CPU path's cos_th)
+    chunks = [list(range(i, min(i + MAX_PAIRS, len(pairs)))) for i in range(0, len(pairs), MAX_PAIRS)]
+    out = {m: {} for m in metrics}
+    with torch.cuda.device(dev):
+        if "precision" in metrics:
+            A, B = _GpuSide(pred, dev), _GpuSide(gt, dev)
+            for ch in chunks:
+                counts = _counts(_match_pass(A, B, [pairs[i] for i in ch], bidirectional, dev)[0], len(ch)) if A.n else [0] * len(ch)
+                for k, i in enumerate(ch):
+                    out["precision"][i] = _ratio(counts[k], A.n)
+        if "recall" in metrics:
+            order = sizes = None
+            if consistency:      # A (the GT) in strand order: CSR runs per strand, strands in ascending id order
+                _, inv, sizes = np.unique(np.asarray(gt.points_id_to_strand_id), return_inverse=True, return_counts=True)
+                order = np.argsort(inv.reshape(-1), kind="stable")
+                offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)).to(dev)
+                b_strand_host = np.unique(np.asarray(pred.points_id_to_strand_id), return_inverse=True)[1].reshape(-1).astype(np.int32)
+                b_strand = torch.from_numpy(b_strand_host).to(dev)
+            A, B = _GpuSide(gt, dev, order), _GpuSide(pred, dev)
+            S = 0 if sizes is None else len(sizes)
+            for ch in chunks:
+                K = len(ch)
+                if A.n == 0:
+                    counts, best = [0] * K, np.zeros((K, S), np.int64)
+                else:
+                    mask, scratch, thr = _match_pass(A, B, [pairs[i] for i in ch], bidirectional, dev)
+                    if consistency:
+                        L = rt.lib()
+                        best_d = torch.zeros((K, S), dtype=torch.int32, device=dev)
+                        over = torch.empty(S, dtype=torch.int32, device=dev)
+                        n_over = torch.zeros(1, dtype=torch.int32, device=dev)
+                        rt.check(L.hgs_strand_votes(rt.current_stream(), S, B.n, K, rt.ptr(A.points), rt.ptr(A.dirs), rt.ptr(offsets),
+                                                    rt.ptr(b_strand), thr.ctypes.data, int(bool(bidirectional)), B.box.ctypes.data,
+                                                    rt.ptr(scratch), int(vote_capacity), rt.ptr(best_d), rt.ptr(over), rt.ptr(n_over)))
+                    counts = _counts(mask, K)
+                    if consistency:
+                        best = best_d.cpu().numpy().astype(np.int64)
+                        off = np.concatenate([[0], np.cumsum(sizes)])
+                        for s in over[:int(n_over.item())].cpu().numpy().tolist():
+                            for k, i in enumerate(ch):
+                                best[k, s] = _host_best(A, off[s], off[s + 1], B, b_strand_host, pairs[i], bidirectional)
+                for k, i in enumerate(ch):
+                    out["recall"][i] = _ratio(counts[k], A.n)
+                    if consistency:
+                        out["strand_consistency"][i] = _consistency(best[k], sizes)
+    return out
 
 
 def compute_eval_data_from_hair_gs(hair_gs, compute_edges=False, only_foreground=False):

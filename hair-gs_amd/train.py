@@ -927,12 +927,15 @@ def main(argv=None):
 
     def evaluate(iteration):
         """The reference's evaluation hook (train.py:229-246): strand metrics against the capture's ground truth, where it
-        has one (hair_eval_data.npz), every eval_frequency iterations and at the end.  CPU code (cKDTree), rank 0 only."""
+        has one (hair_eval_data.npz), every eval_frequency iterations and at the end; rank 0 only.  On the CPU (cKDTree) unless
+        --eval_device names a GPU (csrc/hgs_metrics.hip: the same dict)."""
         import numpy as np
         from loss.metrics import compute_eval_data_from_gs, compute_eval_data_from_hair_gs, compute_metrics
         from scene.hair_gaussian_model import HairGaussianModel
         pred = compute_eval_data_from_hair_gs(g) if isinstance(g, HairGaussianModel) else compute_eval_data_from_gs(g)
-        scene.eval_metrics, scene.eval_thresholds = compute_metrics(pred=pred, gt=scene.gt, bidirectional=bool(opt.bidirectional_eval))
+        dev = getattr(args, "eval_device", "cpu")
+        scene.eval_metrics, scene.eval_thresholds = compute_metrics(pred=pred, gt=scene.gt, bidirectional=bool(opt.bidirectional_eval),
+                                                                    device=None if dev == "cpu" else dev)
         if not args.quiet:
             print(f"[it {iteration}] " + "  ".join(f"{k} {np.round(np.asarray(v), 3).tolist()}" for k, v in scene.eval_metrics.items())
                   + f"  at {scene.eval_thresholds}")

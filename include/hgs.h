@@ -537,6 +537,28 @@ int hgs_strand_walk_ends(void* stream, int n, int n_ep, const long long* pairs, 
 int hgs_strand_walk_fill(void* stream, int S, const long long* starts, const long long* offsets, const unsigned char* flip,
                          const void* nodes, long long* rows, long long* seg_rows, int* id_to_strand);
 
+/* Strand metrics (csrc/hgs_metrics.hip) <-> pct_matched_points of the reference's loss/metrics.py:12-85: the cKDTree
+ *   query_ball_point per (distance, angle) pair, the direction test and the per-point Python loop that counts matches and
+ *   strand-consistency votes.  Points and directions are float64 [n][3]; thresholds_host[K][2] = (r_k, cos_k), 1 <= K <= 32;
+ *   box_host[6] = lo xyz, hi xyz: a box holding every point of B (its per-axis min and max), which must need at most 2^21
+ *   cells of edge max r_k (1 + 1e-6) per axis.
+ * hgs_oriented_match: mask[i] bit k = some B point j has d2 = (dx*dx + dy*dy) + dz*dz <= r_k*r_k (float64, in that order)
+ *   and dot(a_dir_i, b_dir_j) >= cos_k (|dot| when bidirectional; NaN never matches).  Builds a hashed grid of B in scratch
+ *   (>= hgs_oriented_match_scratch_bytes(nB) bytes, 256-byte aligned), which hgs_strand_votes reads afterwards.
+ * hgs_strand_votes: A's S strands are runs of its points, offsets[S+1] (int64); b_strand[nB] = a strand number per B point
+ *   (only equality matters).  best[k][s] = max over B strands b of the number of points of strand s that some point of b
+ *   matches under pair k.  Needs the scratch of an hgs_oriented_match call with the same B, thresholds and box, left
+ *   unchanged.  `capacity` (a power of two <= 2048) sizes the workgroup's LDS tables; a strand whose distinct (point,
+ *   B strand) matches do not fit is appended to overflow[*n_overflow] (*n_overflow device, zero on entry) and its best[.][s]
+ *   is left unwritten: the caller counts it. */
+size_t hgs_oriented_match_scratch_bytes(int nB);
+int hgs_oriented_match(void* stream, int nA, int nB, int K, const double* a_pts, const double* a_dirs, const double* b_pts,
+                       const double* b_dirs, const double* thresholds_host, int bidirectional, const double* box_host,
+                       uint32_t* mask, void* scratch, size_t scratch_bytes);
+int hgs_strand_votes(void* stream, int S, int nB, int K, const double* a_pts, const double* a_dirs, const long long* offsets,
+                     const int* b_strand, const double* thresholds_host, int bidirectional, const double* box_host,
+                     const void* scratch, int capacity, int* best, int* overflow, int* n_overflow);
+
 /* Tile culling (default on).  The reference gives every Gaussian the tiles of its 3-sigma square (forward.cu:229-235,
  * auxiliary.h:46-56) although a pixel only blends it where opacity * exp(power) >= 1/255 (forward.cu:358): with culling on,
  * hgs_forward_preprocess keeps only the tiles that the bounding box of that ellipse reaches, so num_rendered, the tile
