@@ -87,6 +87,9 @@ SIGNATURES = {
     "hgs_oriented_match_scratch_bytes": (sz, [ci]),
     "hgs_oriented_match": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, sz]),
     "hgs_strand_votes": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]),
+    "hgs_orientation_scratch_bytes": (sz, [ci, ci, ci, ci, ci]),
+    "hgs_orientation_field": (ci, [vp, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz]),
+    "hgs_orientation_confidence": (ci, [vp, ci, ci, ci, vp, vp, vp]),
     "hgs_set_tile_cull": (ci, [ci]),
     "hgs_set_segment_policy": (ci, [ci, ci, ci]),
     "hgs_set_row_reduce": (ci, [ci]),

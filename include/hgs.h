@@ -559,6 +559,22 @@ int hgs_strand_votes(void* stream, int S, int nB, int K, const double* a_pts, co
                      const int* b_strand, const double* thresholds_host, int bidirectional, const double* box_host,
                      const void* scratch, int capacity, int* best, int* overflow, int* n_overflow);
 
+/* Orientation maps (csrc/hgs_vision.hip) <-> estimate_orientation_field of the reference's utils/vision.py (cv2.filter2D of A
+ *   Gabor kernels, first argmax, response-weighted angular variance).  N gray uint8 views [N][H][W]; weights[A][side][side]
+ *   float64 (device; the float32 kernel values, row ky, column kx, correlated with the anchor at the centre), side odd and
+ *   <= 63; thetas[A] float64 (device), 2 <= A <= 256.
+ * hgs_orientation_field: r_k = the correlation with BORDER_REFLECT_101, accumulated in float64, rounded half to even and
+ *   saturated to uint8; idx_out[N][H][W] = the first k of the largest r_k; var_out[N][H][W] =
+ *   sum_k (d_k*d_k)*r_k / (sum_k r_k + 1e-7) in k order, d_k = pi/2 - | |thetas[idx] - thetas[k]| - pi/2 |; maxinv_out[N] =
+ *   the largest 1/(var*var) of the view over var != 0 (0: no such pixel).  responses (nullable): [N][H][W][A] uint8 r_k.
+ *   scratch: >= hgs_orientation_scratch_bytes(N, H, W, A, side) bytes, 256-byte aligned.
+ * hgs_orientation_confidence: conf_out[N][H][W] = float((1/(var*var)) / maxinv[n]) where var != 0, else 1. */
+size_t hgs_orientation_scratch_bytes(int N, int H, int W, int A, int side);
+int hgs_orientation_field(void* stream, int N, int H, int W, const unsigned char* gray, int A, int side, const double* weights,
+                          const double* thetas, unsigned char* idx_out, double* var_out, double* maxinv_out, unsigned char* responses,
+                          void* scratch, size_t scratch_bytes);
+int hgs_orientation_confidence(void* stream, int N, int H, int W, const double* var, const double* maxinv, float* conf_out);
+
 /* Tile culling (default on).  The reference gives every Gaussian the tiles of its 3-sigma square (forward.cu:229-235,
  * auxiliary.h:46-56) although a pixel only blends it where opacity * exp(power) >= 1/255 (forward.cu:358): with culling on,
  * hgs_forward_preprocess keeps only the tiles that the bounding box of that ellipse reaches, so num_rendered, the tile
