@@ -199,3 +199,35 @@ def read_points3D_text(path):
         rgb[i] = [int(v) for v in t[4:7]]
         err[i] = float(t[7])
     return xyz, rgb, err
+
+
+def generate_colmap_data(cameras, Es, vertices, vertex_color):
+    """(images, points3D) of a synthetic capture, as the reference's dataset scripts build them: every vertex becomes a 3D point
+    (ids from 1) seen by each camera whose int16 projection (utils.camera.project_opencv) lies in 0 <= x < width, 0 <= y < height;
+    its point2D_idxs are the lengths of those images' keypoint lists after the append (1-based, as the reference writes them);
+    rgb = (color * 255).astype(uint8)[:3]; error 0; images named image_<id>.png with the extrinsics as qvec / tvec."""
+    from utils.camera import project_opencv
+    from utils.transform import rot_to_wxyz_quat
+    pts = np.asarray(vertices)
+    n = pts.shape[0]
+    cam_ids = list(cameras.keys())
+    vis, uv = {}, {}
+    for cid in cam_ids:
+        cam = cameras[cid]
+        xy = project_opencv(cam, Es[cid], pts).reshape(-1, 2)
+        uv[cid] = xy
+        vis[cid] = (xy[:, 0] >= 0) & (xy[:, 0] < cam.width) & (xy[:, 1] >= 0) & (xy[:, 1] < cam.height)
+    rank = {cid: np.cumsum(vis[cid]) for cid in cam_ids}          # list length after each append
+    rgb = (np.asarray(vertex_color) * 255).astype(np.uint8)
+    points = {}
+    for i in range(n):
+        ids = [cid for cid in cam_ids if vis[cid][i]]
+        points[i + 1] = Point3D(id=i + 1, xyz=pts[i], rgb=rgb[i][:3], error=0, image_ids=np.array(ids),
+                                point2D_idxs=[int(rank[cid][i]) for cid in ids])
+    images = {}
+    for cid in cam_ids:
+        E = Es[cid]
+        sel = np.nonzero(vis[cid])[0]
+        images[cid] = BaseImage(id=cid, qvec=rot_to_wxyz_quat(E[:3, :3]), tvec=E[:3, 3], camera_id=cid, name=f"image_{cid}.png",
+                                xys=[uv[cid][k] for k in sel], point3D_ids=[int(k) + 1 for k in sel])
+    return images, points

@@ -90,6 +90,13 @@ SIGNATURES = {
     "hgs_orientation_scratch_bytes": (sz, [ci, ci, ci, ci, ci]),
     "hgs_orientation_field": (ci, [vp, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz]),
     "hgs_orientation_confidence": (ci, [vp, ci, ci, ci, vp, vp, vp]),
+    "hgs_raster_model_bytes": (sz, []),
+    "hgs_raster_vertex_bytes": (sz, []),
+    "hgs_raster_tiles": (ci, [ci, ci]),
+    "hgs_raster_vertices": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, vp]),
+    "hgs_raster_count": (ci, [vp, ci, ci, ci, ci, vp, C.c_longlong, vp, ci, vp, vp, vp]),
+    "hgs_raster_fill": (ci, [vp, ci, ci, ci, ci, vp, C.c_longlong, vp, ci, vp, vp, vp, vp, vp]),
+    "hgs_raster_resolve": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "hgs_set_tile_cull": (ci, [ci]),
     "hgs_set_segment_policy": (ci, [ci, ci, ci]),
     "hgs_set_row_reduce": (ci, [ci]),
@@ -154,6 +161,12 @@ class AdamPrep(C.Structure):
     _fields_ = [("n", ci), ("lr", vp * ADAM_MAX_TENSORS), ("step", vp * ADAM_MAX_TENSORS), ("beta1", cf), ("beta2", cf), ("coef", vp)]
 
 
+class RasterModel(C.Structure):
+    """include/hgs.h HgsRasterModel (an array of them lives in device memory: built here, uploaded as bytes)."""
+    _fields_ = [("draw_base", C.c_longlong), ("idx_offset", C.c_longlong), ("n_prims", ci), ("kind", ci), ("width", ci), ("lit", ci),
+                ("ka", C.c_double), ("kd", C.c_double)]
+
+
 class AdamInline(C.Structure):
     """include/hgs.h HgsAdamInline."""
     _fields_ = [("slot", AdamSlot * 6), ("beta1", cf), ("beta2", cf), ("eps", cf)]
@@ -214,7 +227,8 @@ def lib():
                            "rebuild with hgs_runtime.build()")
         for fn, st in (("hgs_view_targets_bytes", ViewTargets), ("hgs_head_params_bytes", HeadParams),
                        ("hgs_strand_fusion_bytes", StrandFusion), ("hgs_param_backward_bytes", ParamBackward),
-                       ("hgs_adam_prep_bytes", AdamPrep), ("hgs_adam_inline_bytes", AdamInline)):
+                       ("hgs_adam_prep_bytes", AdamPrep), ("hgs_adam_inline_bytes", AdamInline),
+                       ("hgs_raster_model_bytes", RasterModel)):
             if getattr(L, fn)() != C.sizeof(st):
                 raise HgsError(f"{LIB_PATH}: {fn}() = {getattr(L, fn)()} but the binding's struct has {C.sizeof(st)} bytes: "
                                "rebuild with hgs_runtime.build()")

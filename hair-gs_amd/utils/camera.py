@@ -39,3 +39,44 @@ def generate_cameras(number_cameras, height, width, cam_pose=np.eye(4), anchor_p
     cams[number_cameras] = ColmapCamera(number_cameras, "SIMPLE_PINHOLE", width, height,
                                         [focal_length_px, width / 2, height / 2])
     return cams, Es
+
+
+def project_opencv(camera, E, points):
+    """int16 [N, 2] pixel coordinates of world points [N, 3] through a pinhole camera (params[0] = f for both axes, params[1:3] =
+    principal point; no distortion) with world-to-camera extrinsics E, truncated by astype(int16) as the reference does after
+    cv2.projectPoints."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    E = np.asarray(E, dtype=np.float64)
+    pc = p @ E[:3, :3].T + E[:3, 3]
+    f, cx, cy = float(camera.params[0]), float(camera.params[1]), float(camera.params[2])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        uv = np.stack([f * (pc[:, 0] / pc[:, 2]) + cx, f * (pc[:, 1] / pc[:, 2]) + cy], axis=1)
+    return uv.astype(np.int16)
+
+
+def colmap_camera_to_projection_matrix(cam, w=None, h=None, znear=0.01, zfar=5):
+    """Row-major OpenGL perspective matrix of a COLMAP pinhole camera: fov_y = focal2fov(fy, h), aspect w / h (w, h default to
+    twice the principal point), as pyrr's create_perspective_projection builds it (ymax = znear tan(fov_y_deg pi / 360), xmax =
+    ymax aspect, then the frustum from those bounds)."""
+    from .graphics import focal2fov
+    fy, cx, cy = cam.params[0], cam.params[1], cam.params[2]
+    if cam.model != "SIMPLE_PINHOLE":
+        fy, cx, cy = cam.params[1], cam.params[2], cam.params[3]
+    w = cx * 2 if w is None else w
+    h = cy * 2 if h is None else h
+    fovy = np.rad2deg(focal2fov(fy, h))
+    ymax = znear * np.tan(fovy * np.pi / 360.0)
+    xmax = ymax * (w / h)
+    left, right, bottom, top = -xmax, xmax, -ymax, ymax
+    A = (right + left) / (right - left)
+    B = (top + bottom) / (top - bottom)
+    C = -(zfar + znear) / (zfar - znear)
+    D = -2.0 * zfar * znear / (zfar - znear)
+    E = 2.0 * znear / (right - left)
+    F = 2.0 * znear / (top - bottom)
+    return np.array([[E, 0.0, A, 0.0], [0.0, F, B, 0.0], [0.0, 0.0, C, D], [0.0, 0.0, -1.0, 0.0]])
+
+
+def opencv_to_opengl_view_matrix(w2c):
+    """OpenGL view matrix of an OpenCV world-to-camera matrix: the camera's y and z axes flipped, diag(1, -1, -1, 1) w2c."""
+    return np.diag([1.0, -1.0, -1.0, 1.0]) @ np.asarray(w2c, dtype=np.float64)

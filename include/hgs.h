@@ -575,6 +575,41 @@ int hgs_orientation_field(void* stream, int N, int H, int W, const unsigned char
                           void* scratch, size_t scratch_bytes);
 int hgs_orientation_confidence(void* stream, int N, int H, int W, const double* var, const double* maxinv, float* conf_out);
 
+/* Line / triangle rasterizer of the dataset synthesis (csrc/hgs_raster.hip) <-> the reference's OpenGL renderer
+ *   (scene/OpenGLRenderer.py); the contract is scene/mesh_renderer.py's (this project), which both backends meet bit for bit.
+ *   Vertex arrays are the selected models' concatenated, float64: pw[NV][4] = M [p, 1], nw[NV][3] = inv(M3)^T n, col[NV][3];
+ *   idx: uint32 global vertex ids, models[n_models] (device) in list order, draw index = draw_base + primitive.  views / projs:
+ *   [V][16] row-major float64 (device).  vout: V * NV records of hgs_raster_vertex_bytes().  Tiles are 32 x 32 window pixels,
+ *   hgs_raster_tiles(W, H) per view, row-major from the bottom-left.
+ * hgs_raster_vertices: the per-(view, vertex) stage.
+ * hgs_raster_count: tile_counts[V][T] (zeroed by the caller) += tiles each primitive reaches; *dropped (zeroed) += dropped ones.
+ * hgs_raster_fill: list[tile_offsets[vt] + k] = the draw indices of tile vt (tile_offsets: exclusive scan of tile_counts, int64;
+ *   tile_cursor[V][T] zeroed); in no particular order.
+ * hgs_raster_resolve: rgb[V][H][W][3] (image rows top-down), gray[V][H][W] (nullable); light_host: position, ambient rgb, diffuse
+ *   rgb (9 doubles); background_host: 3 bytes. */
+#define HGS_RASTER_MAX_MODELS 64
+typedef struct HgsRasterModel {
+  long long draw_base;          /* draw index of the model's first primitive */
+  long long idx_offset;         /* its first entry in idx */
+  int n_prims, kind;            /* kind: 2 = lines, 3 = triangles */
+  int width, lit;               /* line width in pixels (>= 1); lit: 1 = the diffuse shader, 0 = colour as it is */
+  double ka, kd;
+} HgsRasterModel;
+size_t hgs_raster_model_bytes(void);
+size_t hgs_raster_vertex_bytes(void);
+int hgs_raster_tiles(int W, int H);
+int hgs_raster_vertices(void* stream, int V, int NV, int W, int H, const double* pw, const double* views, const double* projs,
+                        void* vout);
+int hgs_raster_count(void* stream, int V, int W, int H, int n_models, const HgsRasterModel* models, long long n_prims,
+                     const unsigned* idx, int NV, const void* vout, int* tile_counts, unsigned long long* dropped);
+int hgs_raster_fill(void* stream, int V, int W, int H, int n_models, const HgsRasterModel* models, long long n_prims,
+                    const unsigned* idx, int NV, const void* vout, const int* tile_counts, const long long* tile_offsets,
+                    int* tile_cursor, unsigned* list);
+int hgs_raster_resolve(void* stream, int V, int W, int H, int n_models, const HgsRasterModel* models, const unsigned* idx,
+                       int NV, const void* vout, const double* pw, const double* nw, const double* col, const double* light_host,
+                       const unsigned char* background_host, const int* tile_counts, const long long* tile_offsets,
+                       const unsigned* list, unsigned char* rgb, unsigned char* gray);
+
 /* Tile culling (default on).  The reference gives every Gaussian the tiles of its 3-sigma square (forward.cu:229-235,
  * auxiliary.h:46-56) although a pixel only blends it where opacity * exp(power) >= 1/255 (forward.cu:358): with culling on,
  * hgs_forward_preprocess keeps only the tiles that the bounding box of that ellipse reaches, so num_rendered, the tile
