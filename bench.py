@@ -2,7 +2,15 @@
 """bench.py -- headline benchmark: strand-Gaussian training iterations per second (+ forward render ms/view).
 
   python bench.py --gpus N --steps K --warmup W [--workload north_star|c2|c3|c4|c5|tiny] [--scaling weak|strong]
-                  [--dump-outputs DIR]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what its headline needs and nothing more: it sets up the workload, captures the step, runs the W warm-up
+steps, times the K-step regions, writes --dump-outputs and prints the JSON line (`metric`, `value`, `unit`, `ms_per_step`,
+`repeats`, `config` without the list statistics, ...).  Everything else the benchmark measures -- the sustained leg, per-kernel
+timing and the rooflines, forward-render timing and list statistics, the CPU baseline, `trained_state`, `roofline_c3` and
+`pipeline_states` -- runs only with --full, which fills those keys in on the same line; the options that shape them
+(--trained-iters, --sustained-seconds, --no-c3-leg, --no-pipeline-legs, --no-cpu-baseline, --no-kernel-timing) take effect
+under --full only.
 
 One *train iteration* is the reference's (train.py:133-204): lr update, ONE camera view, render + 2 more raster
 passes inside the losses (mask, orientation), backward through all three, densification statistics, Adam step.
@@ -22,10 +30,13 @@ the ranks) is timed --repeats times back to back; `value` / `ms_per_step` are th
 min / median / max.  On one GPU the steps go out --steps-per-graph (default 8) at a time: each is a full optimizer step on
 its own random view, eight of them are captured in one HIP graph and replayed with ONE launch (GraphedStep.step_many: a
 graph launch costs ~8 us of idle GPU whatever it holds; bit-identical to single-step replays); steps that do not fill a
-launch -- and every step with several ranks -- replay the single-step graph.  A `sustained` leg then replays steps for >= --sustained-seconds (default 2 s) in one region, long
-enough for an SMI sampler to see the GPU busy, and reports its own rate.
+launch -- and every step with several ranks -- replay the single-step graph.  With --full a `sustained` leg then replays
+steps for >= --sustained-seconds (default 2 s) in one region, long enough for an SMI sampler to see the GPU busy, and reports
+its own rate.
 
-The JSON line also carries
+With --full the JSON line also carries
+  render_ms_per_view  forward-only render time per view through render() and through gaussian_renderer.frames.FrameRenderer,
+                beside the per-view list statistics in `config` (mean_num_rendered, mean_sum_tile_list_len, ... after tile cull)
   psnr_vs_oracle_db  PSNR of the HIP render of view 0 against the CPU oracle's image of the same parameters (cpu_baseline leg)
   trained_state the same protocol after --trained-iters N (default 1000) iterations of the FULL loop (densification, merging,
                 opacity reset, graph re-captures), beside the headline: the headline times the sparsest state of the workload
@@ -87,22 +98,22 @@ def parse():
     ap.add_argument("--steps-per-graph", type=int, default=8,
                     help="optimizer steps captured per graph launch (GraphedStep.step_many; 1 GPU, one view per step; the "
                          "steps that do not fill a launch replay the single-step graph)")
-    ap.add_argument("--sustained-seconds", type=float, default=2.0, help="length of the sustained leg (0: skip)")
+    ap.add_argument("--sustained-seconds", type=float, default=2.0, help="--full: length of the sustained leg (0: skip)")
     ap.add_argument("--trained-iters", type=int, default=1000,
-                    help="second leg (1 GPU): train this many iterations WITH the topology operators (densification, merging, "
+                    help="--full: second leg (1 GPU): train this many iterations WITH the topology operators (densification, merging, "
                          "opacity reset), then time the same protocol on that state; reported beside the headline as "
                          "`trained_state` (0: skip -- what the rocprofv3 scripts pass, so that their kernel statistics average ONE "
                          "state per kernel)")
     ap.add_argument("--no-c3-leg", action="store_true",
-                    help="skip `roofline_c3`: BASELINE.json config 3 (200k strand-Gaussians) timed by a child process of this run "
+                    help="--full: skip `roofline_c3`: BASELINE.json config 3 (200k strand-Gaussians) timed by a child process of this run "
                          "(rank 0, 1 GPU, north_star workload only)")
     ap.add_argument("--no-pipeline-legs", action="store_true",
-                    help="skip `pipeline_states`: the Stage-I cloud and the merged Stage-III start model of a 200 k-segment capture, "
+                    help="--full: skip `pipeline_states`: the Stage-I cloud and the merged Stage-III start model of a 200 k-segment capture, "
                          "each timed by a child process of this run (rank 0, 1 GPU, north_star workload only)")
     ap.add_argument("--stage1-iters", type=int, default=None,
                     help="--workload stage1_1080p / stage3_merged: iterations of the Stage-I loop before the state is taken")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="disable per-kernel HIP-event timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip `cpu_baseline`")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full: disable per-kernel HIP-event timing")
     ap.add_argument("--three-pass", action="store_true",
                     help="three separate raster passes per iteration like the reference instead of the single 7-channel pass")
     ap.add_argument("--op-by-op", action="store_true", help="the iteration as the reference structures it (getters, render, loss_function as separate autograd ops) instead of the fused strand iteration")
@@ -113,6 +124,9 @@ def parse():
     ap.add_argument("--eager", action="store_true", help="eager dispatch of every kernel instead of replaying the captured HIP graph")
     ap.add_argument("--blocking", action="store_true",
                     help="reference-style forward (host reads num_rendered in every pass) instead of the async capacity mode")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: sustained leg, per-kernel timing and rooflines, render timing "
+                         "and list statistics, CPU baseline, trained state, roofline_c3 and pipeline_states (see the docstring)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed regions, write what the last timed step handed its caller -- its loss and the model "
                          "state it updated in place -- as DIR/<name>.npy (dump_outputs; rank 0)")
@@ -288,7 +302,7 @@ def c3_roofline_leg():
     try:
         cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "c3", "--views", "4", "--steps", "40",
                              "--warmup", "5", "--repeats", "1", "--sustained-seconds", "0", "--trained-iters", "0",
-                             "--no-cpu-baseline", "--no-c3-leg"], capture_output=True, text=True, timeout=300)
+                             "--no-cpu-baseline", "--no-c3-leg", "--full"], capture_output=True, text=True, timeout=300)
         c3 = json.loads(cp.stdout.strip().splitlines()[-1])
         return dict(c3["roofline"], workload=c3["config"]["workload"], iters_per_sec=c3["value"],
                     blend_fwd=c3.get("roofline_blend_fwd"), kernel_us_per_launch=c3.get("kernel_us_per_launch"))
@@ -303,7 +317,7 @@ def pipeline_state_leg(name):
     try:
         cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", "40", "--warmup", "5",
                              "--repeats", "3", "--sustained-seconds", "0", "--trained-iters", "0", "--no-cpu-baseline",
-                             "--no-c3-leg", "--no-pipeline-legs"], capture_output=True, text=True, timeout=600)
+                             "--no-c3-leg", "--no-pipeline-legs", "--full"], capture_output=True, text=True, timeout=600)
         r = json.loads(cp.stdout.strip().splitlines()[-1])
         return {"value": r["value"], "unit": r["unit"], "ms_per_step": r["ms_per_step"], "workload": r["config"]["workload"],
                 "state": r["config"].get("pipeline_state"), "gaussians": r["config"]["gaussians"],
@@ -399,7 +413,7 @@ def main():
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={os.environ.get('WORLD_SIZE')}", file=sys.stderr)
         sys.exit(2)
     c3_leg = pipeline_legs = None
-    side_legs_ok = (int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.workload == "north_star"
+    side_legs_ok = (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.workload == "north_star"
                     and not args.no_kernel_timing and not args.eager and not args.blocking
                     and "rocprof" not in os.environ.get("LD_PRELOAD", "").lower())   # (a profiler's preload has initialised the GPU)
     if side_legs_ok and not args.no_c3_leg:
@@ -630,7 +644,7 @@ def main():
                     inline_adam=bool(use_graph and gs.inline_adam),
                     collective_captured=(gs.collective_captured if use_graph else False))
 
-    head = measure(0, args.sustained_seconds > 0, not args.no_kernel_timing, dump_dir=args.dump_outputs)
+    head = measure(0, args.full and args.sustained_seconds > 0, args.full and not args.no_kernel_timing, dump_dir=args.dump_outputs)
     dt, regions, sustained, kern, kern_steps, fused = (head[k] for k in ("dt", "regions", "sustained", "kern", "kern_steps", "fused"))
 
     def frame_stats():
@@ -706,12 +720,11 @@ def main():
 
         return dict(render_ms=render_ms, render_graph_ms=render_graph_ms, render_graph_equal=same, render_graph_frames=KF, meanL=meanL, meanR=meanR, meanL_culled=meanL_culled, meanR_culled=meanR_culled, tiles_used=tiles_used)
 
-    fs = frame_stats()
-    render_ms, meanL, meanR, meanL_culled, meanR_culled = (fs[k] for k in ("render_ms", "meanL", "meanR", "meanL_culled", "meanR_culled"))
+    fs = frame_stats() if args.full else None
     P_head = model.get_xyz.shape[0]
 
     cpu_result = {}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         threads = min(os.cpu_count() or 1, 64)
         try:
             sec, psnr = cpu_baseline(model, cams[0], threads, bg)
@@ -732,7 +745,7 @@ def main():
     # after initialisation).  N iterations of the full loop -- densification, merging, opacity reset at the reference's
     # intervals, graph re-captures -- then capture / warm-up / regions exactly as above.  Reported beside the headline.
     trained = None
-    if args.trained_iters > 0 and world == 1 and use_graph and not strong:
+    if args.full and args.trained_iters > 0 and world == 1 and use_graph and not strong:
         from train import training
         raster.set_async(not args.blocking)
         opt.enable_topology = True
@@ -791,8 +804,6 @@ def main():
                    "gaussians": P, "views": len(cams), "width": W, "height": H, "parallelism": f"view-parallel x{world}",
                    "pipeline_state": pipeline_info,
                    "views_per_optimizer_step": views_per_step,
-                   "mean_num_rendered": meanR, "mean_sum_tile_list_len": meanL,
-                   "mean_num_rendered_after_tile_cull": meanR_culled, "mean_sum_tile_list_len_after_tile_cull": meanL_culled,
                    "forward_mode": "blocking" if args.blocking else "async-capacity",
                    "dispatch": "hip-graph replay" if use_graph else "eager",
                    "optimizer_steps_per_graph_launch": head["steps_per_graph"],
@@ -800,11 +811,16 @@ def main():
                    # True: no optimizer launch -- the backward's lanes apply Adam to the elements whose gradient they finish
                    "adam_in_backward_lanes": head["inline_adam"],
                    "raster_passes_per_iter": 1 if getattr(opt, "single_pass", True) else 3},
-        "render_ms_per_view": render_ms,                       # render(): the drop-in call, eager, ~20 host-side tensor ops per view
-        "render_ms_per_view_frame_renderer": fs["render_graph_ms"],   # gaussian_renderer.frames: the same frames as one graph per view
-        "frame_renderer_equals_render": fs["render_graph_equal"], "frame_renderer_frames_per_launch": fs["render_graph_frames"],
         "trained_state": trained,
     }
+    if fs is not None:
+        result["config"].update({"mean_num_rendered": fs["meanR"], "mean_sum_tile_list_len": fs["meanL"],
+                                 "mean_num_rendered_after_tile_cull": fs["meanR_culled"],
+                                 "mean_sum_tile_list_len_after_tile_cull": fs["meanL_culled"]})
+        result.update({
+            "render_ms_per_view": fs["render_ms"],                     # render(): the drop-in call, eager, ~20 host-side tensor ops per view
+            "render_ms_per_view_frame_renderer": fs["render_graph_ms"],   # gaussian_renderer.frames: the same frames as one graph per view
+            "frame_renderer_equals_render": fs["render_graph_equal"], "frame_renderer_frames_per_launch": fs["render_graph_frames"]})
     if kern:
         ch = 7 if getattr(opt, "single_pass", True) else 3
         result["roofline"], result["roofline_blend_fwd"] = roofline_block(kern, fs, W, H, ch, args.workload)
