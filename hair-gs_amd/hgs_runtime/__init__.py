@@ -90,6 +90,8 @@ SIGNATURES = {
     "hgs_orientation_scratch_bytes": (sz, [ci, ci, ci, ci, ci]),
     "hgs_orientation_field": (ci, [vp, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz]),
     "hgs_orientation_confidence": (ci, [vp, ci, ci, ci, vp, vp, vp]),
+    "hgs_view_stats_num_blocks": (ci, [ci, ci]),
+    "hgs_view_stats": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, vp, cf, vp, vp]),
     "hgs_raster_model_bytes": (sz, []),
     "hgs_raster_vertex_bytes": (sz, []),
     "hgs_raster_tiles": (ci, [ci, ci]),

@@ -575,6 +575,23 @@ int hgs_orientation_field(void* stream, int N, int H, int W, const unsigned char
                           void* scratch, size_t scratch_bytes);
 int hgs_orientation_confidence(void* stream, int N, int H, int W, const double* var, const double* maxinv, float* conf_out);
 
+/* Image metrics of rendered views against their capture (csrc/hgs_view_stats.hip) <-> loss/image_metrics.py view_metrics (this
+ *   project; the reference has no counterpart), whose CPU path is the contract.  V views of one size, every plane device memory,
+ *   float32 unless stated: pred, gt [V][3][H][W] (pred: the render clamped to [0, 1]); gt_mask [V][H][W] uint8 (nonzero: set), fg
+ *   [V][H][W] (the rendered foreground channel, foreground where >= fg_threshold), omap [V][3][H][W] (rendered world-space
+ *   directions), viewmats [V][16] (world_view_transform, row-major), gt_theta [V][H][W], confidence [V][H][W].  Every plane but pred
+ *   and gt may be NULL and turns its statistics off; the orientation ones need omap, viewmats and gt_theta (its mask: gt_mask,
+ *   else omap != 0 in any channel; no confidence: weight 1).  Per-pixel values are float32 in the CPU path's order, the sums
+ *   float64 in a fixed order: bitwise reproducible, and a view's row does not depend on the other views of the batch.
+ *   partials: V * hgs_view_stats_num_blocks(H, W) * HGS_VIEW_STATS_N doubles of scratch; out [V][HGS_VIEW_STATS_N] doubles:
+ *   sse, sse over the GT mask, GT mask count, foreground count, intersection count, orientation |diff| sum, diff * confidence sum,
+ *   orientation mask count, count of diff <= 10 degrees, count of diff <= 20 degrees. */
+#define HGS_VIEW_STATS_N 10
+int hgs_view_stats_num_blocks(int H, int W);
+int hgs_view_stats(void* stream, int V, int H, int W, const float* pred, const float* gt, const unsigned char* gt_mask, const float* fg,
+                   float fg_threshold, const float* omap, const float* viewmats, const float* gt_theta, const float* confidence,
+                   float min_val, double* partials, double* out);
+
 /* Line / triangle rasterizer of the dataset synthesis (csrc/hgs_raster.hip) <-> the reference's OpenGL renderer
  *   (scene/OpenGLRenderer.py); the contract is scene/mesh_renderer.py's (this project), which both backends meet bit for bit.
  *   Vertex arrays are the selected models' concatenated, float64: pw[NV][4] = M [p, 1], nw[NV][3] = inv(M3)^T n, col[NV][3];
