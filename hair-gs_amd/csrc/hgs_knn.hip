@@ -548,3 +548,176 @@ extern "C" int hgs_strand_walk_fill(void* stream, int S, const long long* starts
   return 0;
 }
 
+
+// ---- strand growth (hgs_strand_grow_plan / hgs_strand_grow_fill) -----------------------------------------------------------------
+// growing() (reference scene/hair_gaussian_model.py:1098-1200) extends every strand tip by one segment in the direction of its last
+// k = min(n_seg, growth_averaging_points) non-collapsed segments; the new segment's attributes are the means of theirs.  The
+// reference loops over the strands in Python (180 us a strand).  Here: one lane per strand decides (plan), the caller numbers the
+// grown strands by a scan, and one wavefront per strand writes (fill: lane c = channel c of the new rows, so the loads of a kept
+// row's attributes are consecutive).  Every value has the reference's float32 bits: numpy evaluates each operation in float32
+// (this file is built with -ffp-contract=off), and its means are sums from +0 divided by the count -- over the leading axis of a
+// [k, C] array one row after the other (directions, f_dc, f_rest), over a contiguous [k] run by numpy's pairwise_sum (the lengths,
+// and the [k, 1] attributes opacity / mask / width, whose reduction numpy runs as one contiguous run): NpRunSum.
+namespace {
+
+struct NpRunSum {            // numpy's float32 add.reduce of a contiguous run of known length n <= 128 (pairwise_sum), from +0
+  int n, t, blk;
+  float r[8], res;
+  __device__ __forceinline__ void init(int n_) { n = n_; t = 0; blk = n_ - (n_ & 7); res = 0.f; }
+  __device__ __forceinline__ void add(float v) {
+    if (n < 8) {
+      res = t == 0 ? v : res + v;
+    } else if (t < blk) {
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        if (j == (t & 7)) r[j] = t < 8 ? v : r[j] + v;
+      if (t == blk - 1) res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    } else {
+      res = res + v;
+    }
+    t++;
+  }
+  __device__ __forceinline__ float total() const { return 0.f + res; }
+};
+
+__device__ __forceinline__ bool grow_segment(const long long* __restrict__ rows, long long row, const float* __restrict__ ep, int n_ep,
+                                             float* d, float* len) {
+  const long long a = rows[2 * row], b = rows[2 * row + 1];
+  if (a < 0 || b < 0 || a >= n_ep || b >= n_ep) return false;
+#pragma unroll
+  for (int c = 0; c < 3; c++) d[c] = ep[3 * b + c] - ep[3 * a + c];
+  *len = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);      // np.linalg.norm(axis=1) of 3 components
+  return true;
+}
+
+// status[s]: 0 not grown (at num_points_strand, or every one of the last k segments collapsed), 1 grown, 2 not grown because its tip
+// endpoint is shared with another row of the table (deg != 1), 3 an id out of range; keep[s] bit j: row o1 - k + j is kept
+__global__ __launch_bounds__(256) void grow_plan_kernel(int S, const long long* __restrict__ offsets, const long long* __restrict__ rows,
+                                                        const float* __restrict__ ep, int n_ep, const long long* __restrict__ deg, int n_deg,
+                                                        int max_seg, int k_avg, float min_val, int* __restrict__ status,
+                                                        unsigned* __restrict__ keep, float* __restrict__ mean_len) {
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= S) return;
+  const long long o0 = offsets[s], o1 = offsets[s + 1], n = o1 - o0;
+  int st = 0, cnt = 0;
+  unsigned bits = 0;
+  float ml = 0.f;
+  if (n > 0 && n < max_seg) {
+    const int k = (int)(n < k_avg ? n : k_avg);
+    for (int j = 0; j < k; j++) {
+      float d[3], len;
+      if (!grow_segment(rows, o1 - k + j, ep, n_ep, d, &len)) { st = 3; break; }
+      if (!(len < min_val)) { bits |= 1u << j; cnt++; }
+    }
+    if (st == 0 && cnt > 0) {
+      NpRunSum acc;
+      acc.init(cnt);
+      for (int j = 0; j < k; j++) {
+        if (!((bits >> j) & 1u)) continue;
+        float d[3], len;
+        grow_segment(rows, o1 - k + j, ep, n_ep, d, &len);
+        acc.add(len);
+      }
+      ml = acc.total() / (float)cnt;
+      const long long tip = rows[2 * (o1 - 1) + 1];
+      st = (tip < n_deg && deg[tip] == 1) ? 1 : 2;
+    }
+  }
+  status[s] = st;
+  keep[s] = bits;
+  mean_len[s] = ml;
+}
+
+// one wavefront per strand; channel c of the new row: 0-2 the endpoint, 3-5 f_dc, then f_rest, opacity, mask, width
+__global__ __launch_bounds__(256) void grow_fill_kernel(int S, const long long* __restrict__ offsets, const long long* __restrict__ rows,
+                                                        const long long* __restrict__ seg_rows, int P, const int* __restrict__ status,
+                                                        const int* __restrict__ rank, const unsigned* __restrict__ keep, int k_avg,
+                                                        const float* __restrict__ ep, int n_ep, float growth_length,
+                                                        const float* __restrict__ length_src, const float* __restrict__ f_dc,
+                                                        const float* __restrict__ f_rest, int R, const float* __restrict__ opacity,
+                                                        const float* __restrict__ mask, const float* __restrict__ width,
+                                                        long long* __restrict__ new_pairs, float* __restrict__ new_ep,
+                                                        float* __restrict__ new_dc, float* __restrict__ new_rest,
+                                                        float* __restrict__ new_opacity, float* __restrict__ new_mask,
+                                                        float* __restrict__ new_width) {
+  const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (s >= S || status[s] != 1) return;
+  const long long o1 = offsets[s + 1], n = o1 - offsets[s];
+  const int k = (int)(n < k_avg ? n : k_avg), r = rank[s];
+  const unsigned bits = keep[s];
+  const int cnt = __popc(bits);
+  const long long tip = rows[2 * (o1 - 1) + 1];
+  if (lane == 0) { new_pairs[2 * (long long)r] = tip; new_pairs[2 * (long long)r + 1] = (long long)n_ep + r; }
+  const int C = 9 + R;
+  for (int c = lane; c < C; c += 64) {
+    if (c < 3) {
+      float acc = 0.f;
+      for (int j = 0; j < k; j++) {
+        if (!((bits >> j) & 1u)) continue;
+        float d[3], len;
+        grow_segment(rows, o1 - k + j, ep, n_ep, d, &len);
+        acc = acc + (c == 0 ? d[0] : c == 1 ? d[1] : d[2]) / len;
+      }
+      const float dir = acc / (float)cnt;
+      const float L = length_src ? length_src[0] : growth_length;
+      new_ep[3 * (long long)r + c] = ep[3 * tip + c] + dir * L;
+      continue;
+    }
+    const bool run = c >= 6 + R;                 // [k, 1] attributes: numpy reduces them as one contiguous run
+    const float* src;
+    float* dst;
+    int w, off;
+    if (c < 6) { src = f_dc; dst = new_dc; w = 3; off = c - 3; }
+    else if (!run) { src = f_rest; dst = new_rest; w = R; off = c - 6; }
+    else if (c == 6 + R) { src = opacity; dst = new_opacity; w = 1; off = 0; }
+    else if (c == 7 + R) { src = mask; dst = new_mask; w = 1; off = 0; }
+    else { src = width; dst = new_width; w = 1; off = 0; }
+    NpRunSum pw;
+    pw.init(cnt);
+    float acc = 0.f;
+    for (int j = 0; j < k; j++) {
+      if (!((bits >> j) & 1u)) continue;
+      const long long g = seg_rows[o1 - k + j];
+      const float v = (g >= 0 && g < P) ? src[g * w + off] : 0.f;
+      if (run) pw.add(v);
+      else acc = acc + v;
+    }
+    dst[(long long)r * w + off] = (run ? pw.total() : acc) / (float)cnt;
+  }
+}
+
+}  // namespace
+
+extern "C" int hgs_strand_grow_plan(void* stream, int S, const long long* offsets, const long long* rows, const float* endpoints, int n_ep,
+                                    const long long* deg, int n_deg, int max_segments, int k_avg, float min_val, int* status,
+                                    unsigned* keep, float* mean_len) {
+  if (S < 0 || n_ep < 0 || n_deg < 0) { hgs_set_error("hgs_strand_grow_plan: bad sizes"); return 1; }
+  if (k_avg < 1 || k_avg > 32) { hgs_set_error("hgs_strand_grow_plan: k_avg = %d outside [1, 32]", k_avg); return 1; }
+  if (S == 0) return 0;
+  if (!offsets || !status || !keep || !mean_len || (n_ep > 0 && !endpoints) || (n_deg > 0 && !deg)) {
+    hgs_set_error("hgs_strand_grow_plan: null argument"); return 1;
+  }
+  hipLaunchKernelGGL(grow_plan_kernel, dim3((S + 255) / 256), dim3(256), 0, (hipStream_t)stream, S, offsets, rows, endpoints, n_ep, deg,
+                     n_deg, max_segments, k_avg, min_val, status, keep, mean_len);
+  HGS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int hgs_strand_grow_fill(void* stream, int S, const long long* offsets, const long long* rows, const long long* seg_rows, int P,
+                                    const int* status, const int* rank, const unsigned* keep, int k_avg, const float* endpoints, int n_ep,
+                                    float growth_length, const float* length_src, const float* f_dc, const float* f_rest, int rest_floats,
+                                    const float* opacity, const float* mask, const float* width, long long* new_pairs, float* new_endpoints,
+                                    float* new_f_dc, float* new_f_rest, float* new_opacity, float* new_mask, float* new_width) {
+  if (S < 0 || P < 0 || n_ep < 0 || rest_floats < 0) { hgs_set_error("hgs_strand_grow_fill: bad sizes"); return 1; }
+  if (k_avg < 1 || k_avg > 32) { hgs_set_error("hgs_strand_grow_fill: k_avg = %d outside [1, 32]", k_avg); return 1; }
+  if (S == 0) return 0;
+  if (!offsets || !rows || !seg_rows || !status || !rank || !keep || !endpoints || !f_dc || !opacity || !mask || !width || !new_pairs ||
+      !new_endpoints || !new_f_dc || !new_opacity || !new_mask || !new_width || (rest_floats > 0 && (!f_rest || !new_f_rest))) {
+    hgs_set_error("hgs_strand_grow_fill: null argument"); return 1;
+  }
+  hipLaunchKernelGGL(grow_fill_kernel, dim3((S + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, offsets, rows, seg_rows, P, status, rank,
+                     keep, k_avg, endpoints, n_ep, growth_length, length_src, f_dc, f_rest, rest_floats, opacity, mask, width, new_pairs,
+                     new_endpoints, new_f_dc, new_f_rest, new_opacity, new_mask, new_width);
+  HGS_CHECK_LAUNCH();
+  return 0;
+}

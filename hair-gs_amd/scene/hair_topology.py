@@ -1,6 +1,6 @@
 """Strand topology operators of the Stage-III model (counterparts of the reference's
 scene/hair_gaussian_model.py:619-706 merge_endpoint_pairs, :712-784 index helpers, :788-1077 densification =
-clone / split / merge-collapsed / prune, :1079-1096 merging, :1205-1362 compute_endpoint_pair_to_merge, :1500-1515
+clone / split / merge-collapsed / prune, :1079-1096 merging, :1098-1200 growing, :1205-1362 compute_endpoint_pair_to_merge, :1500-1515
 clean_gaussians).  Mixed into HairGaussianModel.  They run every `densification_interval` / `merge_interval` = 100
 iterations on replicated state.  The reference loops over CUDA tensors element by element (:1246-1253); here the candidate
 search is one query (kd-tree on the CPU, hgs_radius_pairs on the GPU, where the candidates also stay on the device up to the
@@ -16,6 +16,38 @@ def _info_dict(info):
     """The strategies take the reference's `training_info` (an object with a `densification_info` dict, utils/logging.py) or
     the dict itself."""
     return getattr(info, "densification_info", info)
+
+
+def _seq_sum(x, cnt):
+    """Sum over axis 1 of x [G, k, C] (float32) of the first cnt[g] entries, one after the other from +0: numpy's add.reduce over
+    the leading axis of a [k, C] array (np.mean(a, axis=0) of the reference's direction, f_dc and f_rest rows)."""
+    acc = np.zeros((x.shape[0], x.shape[2]), np.float32)
+    for t in range(x.shape[1]):
+        acc = np.where((t < cnt)[:, None], acc + x[:, t], acc)
+    return acc
+
+
+def _run_sum(x, cnt):
+    """Sum of the first cnt[g] entries of every row of x [G, k] (float32) as numpy sums a contiguous run of that length
+    (pairwise_sum, n <= 128: sequential below 8 entries, else 8 partial sums combined pairwise and the rest added), from +0."""
+    out = np.zeros(x.shape[0], np.float32)
+    for c in np.unique(cnt):
+        sel = cnt == c
+        v = x[sel, :c]
+        if c < 8:
+            res = v[:, 0].copy()
+            for t in range(1, c):
+                res = res + v[:, t]
+        else:
+            blk = c - c % 8
+            r = v[:, :8].copy()
+            for i in range(8, blk, 8):
+                r = r + v[:, i:i + 8]
+            res = ((r[:, 0] + r[:, 1]) + (r[:, 2] + r[:, 3])) + ((r[:, 4] + r[:, 5]) + (r[:, 6] + r[:, 7]))
+            for t in range(blk, c):
+                res = res + v[:, t]
+        out[sel] = np.float32(0) + res
+    return out
 
 
 class HairTopologyMixin:
@@ -234,9 +266,162 @@ class HairTopologyMixin:
         self.compute_strands_info()
         self._storage_dirty = True
 
-    def growing(self, training_info=None, **_):
-        raise NotImplementedError("the reference's growing() cannot run either (cat_segments is called without "
-                                  "`new_masks`, hair_gaussian_model.py:1187-1194) and its interval is 100000 iterations")
+    # ---- growth (reference :1098-1200) ---------------------------------------------------------------------------------
+    GROWTH_MAX_AVERAGING = 32       # (the kept rows of a strand's last k segments travel as one 32-bit mask)
+
+    def growing(self, training_info=None, growth_length=0.002, strands_info_is_current=False):
+        """Extend every strand tip by one segment (reference :1098-1200).  For each strand of compute_strands_info(), in strand
+        order: skip it if it has >= num_points_strand segments; of its last k = min(n_seg, growth_averaging_points) segments keep
+        those at least min_val long (none left: skip); the new endpoint is tip + mean(d / |d|) * growth_length, the new segment
+        (tip, n_endpoints + c) -- c counts the strands grown so far -- and its f_dc, f_rest, opacity, mask and width are the means
+        of the kept segments' raw values; everything is appended by cat_segments (zero Adam moments, statistics reset).
+        growth_length None: the mean kept length of the first strand that grows, for it and every later one (the reference
+        overwrites its argument once).  Every value has the bits of the reference's numpy float32 arithmetic
+        (tests/test_growth_cpu.py, tests/golden/ref_growth_pins.npz).
+        Deliberate deviations: (a) the masks are passed to cat_segments (the reference computes them and leaves them out, which
+        raises); (b) the attributes are averaged over the strand's rows of the WHOLE segment table (the reference indexes them
+        with foreground-filtered row numbers; the two agree whenever no background segment exists); (c) a tip whose endpoint
+        another row of the table also uses (a background segment) is not grown -- it would get degree 3 -- and is counted in
+        densification_info["grow_skipped_shared_tip"]; (d) strands_info is recomputed and the storage marked for the spatial
+        sort afterwards (the reference leaves it stale until its next merge).
+        strands_info_is_current: the caller has just recomputed the walk (densification / merging in the same iteration) -- the
+        reference takes whatever strands_info it holds.  On the GPU the decisions and the new rows come from
+        hgs_strand_grow_plan / _fill (HGS_GROWTH=host: the numpy form below, for A/B)."""
+        k_avg = int(self.training_args.growth_averaging_points)
+        if not 1 <= k_avg <= self.GROWTH_MAX_AVERAGING:
+            raise ValueError(f"growth_averaging_points = {k_avg}: growing() averages 1 to {self.GROWTH_MAX_AVERAGING} segments")
+        if not strands_info_is_current or self.strands_info is None:
+            self.compute_strands_info()
+        dev_tables = getattr(self, "_strands_dev", None)
+        if self._endpoints.is_cuda and dev_tables is not None and dev_tables[0].numel() == len(self.strands_info.offsets) \
+                and os.environ.get("HGS_GROWTH", "device") == "device":
+            grown, shared, new = self._grow_device(k_avg, growth_length)
+        else:
+            grown, shared, new = self._grow_host(k_avg, growth_length)
+        info = _info_dict(training_info)
+        if info is not None:
+            info["grow"] = grown
+            info["grow_skipped_shared_tip"] = shared
+        if grown == 0:
+            return                      # nothing grew: the model and its strands are what they were
+        self.cat_segments(*new)
+        self.compute_strands_info()
+        self._storage_dirty = True
+
+    def _strand_global_rows(self):
+        """Row of the whole segment table behind every strand row of strands_info (whose segment_rows index the foreground rows)."""
+        dev_tables = getattr(self, "_strands_dev", None)
+        if dev_tables is not None and dev_tables[2].shape[0] == len(self.strands_info.segment_rows):
+            return dev_tables[2].cpu().numpy()
+        fg = np.nonzero(self.compute_foreground_mask().cpu().numpy())[0]
+        return fg[np.asarray(self.strands_info.segment_rows, np.int64)]
+
+    def _grow_device(self, k_avg, growth_length):
+        """growing()'s decisions and new rows on the device: (grown, skipped shared tips, cat_segments arguments)."""
+        import hgs_runtime as rt
+        offsets, rows, seg_rows = self._strands_dev
+        dev = self._endpoints.device
+        S = int(offsets.numel()) - 1
+        ep = self._endpoints.detach().contiguous()
+        deg = self._endpoint_degree_table().contiguous()
+        i32 = dict(dtype=torch.int32, device=dev)
+        status, keep = torch.empty(S, **i32), torch.empty(S, **i32)
+        mean_len = torch.empty(S, dtype=torch.float32, device=dev)
+        L = rt.lib()
+        with torch.cuda.device(dev):
+            rt.check(L.hgs_strand_grow_plan(rt.current_stream(), S, rt.ptr(offsets), rt.ptr(rows), rt.ptr(ep), int(ep.shape[0]), rt.ptr(deg),
+                                            int(deg.shape[0]), int(self.training_args.num_points_strand), k_avg, float(self.min_val),
+                                            rt.ptr(status), rt.ptr(keep), rt.ptr(mean_len)))
+            flag = (status == 1).to(torch.int32)
+            rank = torch.cumsum(flag, dim=0, dtype=torch.int32)     # (numbered by the scan: the same on every rank and every run)
+            counts = torch.stack([rank[-1], (status == 2).sum().to(torch.int32), (status == 3).sum().to(torch.int32)]).cpu() \
+                if S else torch.zeros(3, dtype=torch.int32)
+            grown, shared, bad = (int(x) for x in counts)
+            if bad:
+                raise RuntimeError(f"growing(): {bad} strands name endpoint ids outside the endpoint table")
+            if grown == 0:
+                return 0, shared, None
+            rank -= flag
+            length_src = None
+            if growth_length is None:
+                length_src = mean_len.index_select(0, torch.argmax(flag).reshape(1))     # (first grown strand: argmax's first maximum)
+            P = int(self.endpoint_pairs.shape[0])
+            dc, rest = self._features_dc.detach().contiguous(), self._features_rest.detach().contiguous()
+            op, mk, wd = (t.detach().contiguous() for t in (self._opacity, self._mask, self._width))
+            R = int(rest[0].numel()) if P else 0
+            f32 = dict(dtype=torch.float32, device=dev)
+            new_pairs = torch.empty((grown, 2), dtype=torch.int64, device=dev)
+            new_ep = torch.empty((grown, 3), **f32)
+            new_dc, new_rest = torch.empty((grown,) + tuple(dc.shape[1:]), **f32), torch.empty((grown,) + tuple(rest.shape[1:]), **f32)
+            new_op, new_mk, new_wd = (torch.empty((grown,) + tuple(t.shape[1:]), **f32) for t in (op, mk, wd))
+            rt.check(L.hgs_strand_grow_fill(rt.current_stream(), S, rt.ptr(offsets), rt.ptr(rows), rt.ptr(seg_rows), P, rt.ptr(status),
+                                            rt.ptr(rank), rt.ptr(keep), k_avg, rt.ptr(ep), int(ep.shape[0]),
+                                            float(growth_length) if growth_length is not None else 0.0, rt.ptr(length_src),
+                                            rt.ptr(dc), rt.ptr(rest), R, rt.ptr(op), rt.ptr(mk), rt.ptr(wd), rt.ptr(new_pairs),
+                                            rt.ptr(new_ep), rt.ptr(new_dc), rt.ptr(new_rest), rt.ptr(new_op), rt.ptr(new_mk),
+                                            rt.ptr(new_wd)))
+        return grown, shared, (new_pairs, new_ep, new_dc, new_rest, new_op, new_mk, new_wd)
+
+    def _grow_host(self, k_avg, growth_length):
+        """growing()'s decisions and new rows in numpy, vectorised over the strands (the form the device path is tested against)."""
+        si = self.strands_info
+        offsets = np.asarray(si.offsets, np.int64)
+        S = len(offsets) - 1
+        if S == 0:
+            return 0, 0, None
+        rows = np.asarray(si.rows, np.int64).reshape(-1, 2)
+        g_rows = self._strand_global_rows()
+        ep = self._endpoints.detach().cpu().numpy()
+        deg = self._endpoint_degree_table().cpu().numpy()
+        n = offsets[1:] - offsets[:-1]
+        k = np.minimum(n, k_avg)
+        j = np.arange(k_avg)
+        valid = j[None, :] < k[:, None]
+        at = np.where(valid, offsets[1:, None] - k[:, None] + j[None, :], 0)          # [S, k_avg] strand rows, root -> tip
+        d = ep[rows[at, 1]] - ep[rows[at, 0]]
+        norm = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+        kept = valid & ~(norm < np.float32(self.min_val))
+        cnt = kept.sum(axis=1)
+        tip = rows[offsets[1:] - 1, 1]
+        cand = (n > 0) & (n < int(self.training_args.num_points_strand)) & (cnt > 0)
+        tip_free = deg[tip] == 1
+        grow = np.nonzero(cand & tip_free)[0]
+        shared = int((cand & ~tip_free).sum())
+        if grow.size == 0:
+            return 0, shared, None
+        # the kept rows of every grown strand, packed to the front in strand order
+        order = np.argsort(~kept[grow], axis=1, kind="stable")
+        pk = np.take_along_axis(at[grow], order, axis=1)
+        cg = cnt[grow]
+        G, kmax = grow.size, int(cg.max())
+        pk = pk[:, :kmax]
+        live = np.arange(kmax)[None, :] < cg[:, None]
+        dd = np.take_along_axis(d[grow], order[..., None], axis=1)[:, :kmax]
+        nn = np.take_along_axis(norm[grow], order, axis=1)[:, :kmax]
+        u = np.where(live[..., None], dd / np.where(live, nn, np.float32(1))[..., None], np.float32(0))
+        cnt_f = cg.astype(np.float32)
+        direction = _seq_sum(u, cg) / cnt_f[:, None]
+        if growth_length is None:
+            length = _run_sum(nn[:1], cg[:1])[0] / cnt_f[0]
+        else:
+            length = np.float32(growth_length)
+        new_ep = ep[tip[grow]] + direction * length
+        n_ep = int(self._endpoints.shape[0])
+        new_pairs = np.stack([tip[grow], n_ep + np.arange(G, dtype=np.int64)], axis=1)
+        gr = g_rows[pk]                                                              # [G, kmax] rows of the whole table
+        out = []
+        for t in (self._features_dc, self._features_rest, self._opacity, self._mask, self._width):
+            v = t.detach().cpu().numpy()
+            flat = v.reshape(v.shape[0], -1)
+            vals = flat[gr]                                                          # [G, kmax, C]
+            if flat.shape[1] == 1:        # [k, 1]: numpy reduces it as one contiguous run (pairwise_sum)
+                mean = _run_sum(vals[..., 0], cg)[:, None] / cnt_f[:, None]
+            else:
+                mean = _seq_sum(vals, cg) / cnt_f[:, None]
+            out.append(torch.from_numpy(np.ascontiguousarray(mean.reshape((G,) + v.shape[1:]), dtype=np.float32)).to(self.device))
+        new_pairs_t = torch.from_numpy(new_pairs).to(self.device)
+        new_ep_t = torch.from_numpy(np.ascontiguousarray(new_ep, dtype=np.float32)).to(self.device)
+        return G, shared, (new_pairs_t, new_ep_t, *out)
 
     def compute_endpoint_pair_to_merge(self, chunk_size=-1, max_num_nn=-1):
         """Greedy one-to-one matching of nearby strand ends (root/tip) that face each other: candidates = foreground

@@ -278,8 +278,12 @@ def _training_step(gaussians, viewpoint_cam, opt, bg, iteration, extent, vp, ras
                 if info is not None:
                     info.densification_info["opacity_reset"] = 1
         if isinstance(gaussians, HairGaussianModel) and getattr(opt, "enable_topology", True):
-            if iteration % opt.merge_interval == 0 and hasattr(gaussians, "merging"):
+            merged = iteration % opt.merge_interval == 0 and hasattr(gaussians, "merging")
+            if merged:
                 gaussians.merging(training_info=info, strands_info_is_current=densified)
+            if iteration % opt.growth_interval == 0 and hasattr(gaussians, "growing"):
+                # (reference train.py:195-200: right after merging; a densification or merge of this iteration has just walked the strands)
+                gaussians.growing(training_info=info, strands_info_is_current=densified or merged)
             if getattr(gaussians, "_storage_dirty", False):
                 gaussians._maybe_sort_spatially()     # back to strand order, once per iteration (scene/hair_gaussian_model.py)
         if info is not None and info.densification_info:
@@ -696,6 +700,8 @@ def topology_due(gaussians, opt, iteration):
             due.append("reset_opacity")
     if isinstance(gaussians, HairGaussianModel) and iteration % opt.merge_interval == 0:
         due.append("merge")
+    if isinstance(gaussians, HairGaussianModel) and iteration % opt.growth_interval == 0:
+        due.append("grow")
     if iteration % 1000 == 0 and gaussians.active_sh_degree < gaussians.max_sh_degree:
         due.append("sh")
     return due

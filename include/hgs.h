@@ -46,9 +46,9 @@ extern "C" {
  * 5, round 5: hgs_backward_multi_params / hgs_hair_endpoint_gather, HgsPrologue.adam_prep and the in-lane Adam update, and the contract that HgsHeadParams.tile_used also limits
  * what hgs_loss_head_forward writes of d_extra_unit -- a caller of version 4 that read those planes everywhere must not;
  * 6, round 6: tile_delta in the image buffer; 7: every image-buffer field behind tile_cursor starts on a 256-byte boundary, and a
- * misaligned HgsHeadParams.tile_used is an error of hgs_loss_head_forward);
+ * misaligned HgsHeadParams.tile_used is an error of hgs_loss_head_forward; 8: hgs_strand_grow_plan / hgs_strand_grow_fill);
  * the Python binding refuses a library whose version or struct sizes differ from its own */
-#define HGS_ABI_VERSION 7
+#define HGS_ABI_VERSION 8
 #define HGS_TILE 16 /* cuda_rasterizer/config.h:16-17 */
 
 int hgs_abi_version(void);
@@ -536,6 +536,24 @@ int hgs_nearest_distance_f64(void* stream, int N, int M, const float* points, co
 int hgs_strand_walk_ends(void* stream, int n, int n_ep, const long long* pairs, int* deg, void* nodes, int* other, int* len, int* flags);
 int hgs_strand_walk_fill(void* stream, int S, const long long* starts, const long long* offsets, const unsigned char* flip,
                          const void* nodes, long long* rows, long long* seg_rows, int* id_to_strand);
+/* hgs_strand_grow_plan / hgs_strand_grow_fill <-> growing() of the Stage-III model (scene/hair_gaussian_model.py:1098-1200), on the
+ *   strands of hgs_strand_walk_fill (offsets[S+1], rows[total][2] root -> tip, seg_rows[total]: row of the whole segment table).
+ *   _plan, one lane per strand: status[s] = 1 if strand s grows, 0 if it has >= max_segments segments or every one of its last
+ *   k = min(n_seg, k_avg) segments is shorter than min_val, 2 if it would grow but its tip id has deg[tip] != 1 (deg[n_deg]: segments
+ *   per endpoint id over the whole table), 3 if an id of its rows is outside [0, n_ep); keep[s] bit j = row offsets[s+1] - k + j is
+ *   kept (1 <= k_avg <= 32); mean_len[s] = mean length of the kept segments (numpy's float32 pairwise sum / count).
+ *   _fill, one wavefront per strand, for the strands with status 1: rank[s] = exclusive prefix count of the grown strands (the
+ *   caller's scan), the new row r = rank[s] is pair (tip, n_ep + r), endpoint tip + mean(d / |d|) * L (L = *length_src if
+ *   length_src is not NULL, else growth_length) and the means of the kept rows' f_dc [P][3], f_rest [P][rest_floats], opacity,
+ *   mask, width [P]; every value has the bits of the reference's numpy float32 arithmetic.  No atomics: deterministic. */
+int hgs_strand_grow_plan(void* stream, int S, const long long* offsets, const long long* rows, const float* endpoints, int n_ep,
+                         const long long* deg, int n_deg, int max_segments, int k_avg, float min_val, int* status, unsigned* keep,
+                         float* mean_len);
+int hgs_strand_grow_fill(void* stream, int S, const long long* offsets, const long long* rows, const long long* seg_rows, int P,
+                         const int* status, const int* rank, const unsigned* keep, int k_avg, const float* endpoints, int n_ep,
+                         float growth_length, const float* length_src, const float* f_dc, const float* f_rest, int rest_floats,
+                         const float* opacity, const float* mask, const float* width, long long* new_pairs, float* new_endpoints,
+                         float* new_f_dc, float* new_f_rest, float* new_opacity, float* new_mask, float* new_width);
 
 /* Strand metrics (csrc/hgs_metrics.hip) <-> pct_matched_points of the reference's loss/metrics.py:12-85: the cKDTree
  *   query_ball_point per (distance, angle) pair, the direction test and the per-point Python loop that counts matches and
