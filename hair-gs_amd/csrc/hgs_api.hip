@@ -101,13 +101,6 @@ __global__ __launch_bounds__(256) void densify_stats_kernel(int P, const int* __
   denom[i] += 1.f;
 }
 
-static int g_tile_cull = 1;
-extern "C" int hgs_set_tile_cull(int on) {
-  const int was = g_tile_cull;
-  g_tile_cull = on != 0;
-  return was;
-}
-
 static int check_aligned(const void* p, const char* what) {
   if (!p || ((size_t)p & (HGS_ALIGN - 1))) {
     hgs_set_error("%s must be a non-null %d-byte aligned device pointer", what, HGS_ALIGN);
@@ -123,10 +116,17 @@ const char* hgs_last_error(void) { return g_err; }
 
 size_t hgs_geom_bytes(int P) { HgsGeom g; return hgs_geom_carve(nullptr, (size_t)(P > 0 ? P : 0), g, nullptr); }
 size_t hgs_image_bytes(int W, int H) { HgsImage im; return hgs_image_carve(nullptr, (size_t)W, (size_t)H, im, nullptr); }
-size_t hgs_binning_bytes(int R) { HgsBinning b; return hgs_binning_carve(nullptr, (size_t)(R > 0 ? R : 0), b, nullptr); }
-size_t hgs_backward_scratch_bytes(int P, int R) {
-  (void)P;
-  return hgs_align_up((size_t)(R > 0 ? R : 0) * HGS_INST_GRAD_FLOATS * sizeof(float)) + HGS_ALIGN;
+size_t hgs_binning_bytes(int R, int channels) {
+  if (channels != 3 && channels != 7) return 0;
+  HgsBinning b;
+  return hgs_binning_carve(nullptr, (size_t)(R > 0 ? R : 0), b, nullptr, channels);
+}
+size_t hgs_backward_scratch_bytes(int P, int R, int channels) {
+  const size_t p = (size_t)(P > 0 ? P : 0), r = (size_t)(R > 0 ? R : 0);
+  if (channels == 3) return hgs_align_up(r * HGS_INST_GRAD_FLOATS * sizeof(float)) + HGS_ALIGN;
+  // 7 channels: R instance rows of 16 floats, then (256-byte aligned) row_reduce_kernel's per-Gaussian sums and per-run partial sums
+  if (channels == 7) return hgs_align_up(r * 16 * sizeof(float)) + hgs_align_up(hgs_row_reduce_floats(p, r) * sizeof(float)) + HGS_ALIGN;
+  return 0;
 }
 int hgs_geom_layout(int P, size_t* offsets) { HgsGeom g; hgs_geom_carve(nullptr, (size_t)P, g, offsets); return 0; }
 int hgs_image_zero_range(int W, int H, size_t* offset, size_t* bytes) {
@@ -255,7 +255,7 @@ static int forward_preprocess_impl(void* stream, int P, int D, int M, int W, int
   a.rotations = rotations; a.cov3D_precomp = cov3D_precomp; a.viewmatrix = viewmatrix; a.projmatrix = projmatrix;
   a.campos = campos; a.scale_modifier = scale_modifier; a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
   a.prefiltered = prefiltered & 1;
-  a.tile_cull = g_tile_cull;
+  a.tile_cull = (prefiltered & HGS_TILE_CULL) ? 1 : 0;
   a.row_runs = (prefiltered & HGS_COUNT_ROW_RUNS) ? 1 : 0;
   // Capacity mode (nobody waits for num_rendered here) with a place to report the count: the scan is left to the
   // scatter kernel of hgs_forward_render (scatter_kernel, "fused scan").  A blocking caller needs the count NOW.
@@ -285,23 +285,15 @@ static int forward_preprocess_impl(void* stream, int P, int D, int M, int W, int
   return 0;
 }
 
-// How the blend kernels get their records (hgs_common.h, HgsBinning::lazy): 1 always from the templates, 0 always packed by the sort
-// kernel, -1 (default) by the pass's entries per tile.
-static int g_lazy_mode = -1;
-extern "C" int hgs_set_lazy_records(int mode) {
-  const int was = g_lazy_mode;
-  g_lazy_mode = mode > 0 ? 1 : (mode < 0 ? -1 : 0);
-  return was;
-}
-
-static int forward_render_impl(void* stream, int P, int W, int H, int R_capacity, const float* bg,
-                               const float* colors_precomp, const float* extra, int n_extra, void* geom_buf,
-                               void* binning_buf, void* image_buf, float* out_color) {
+int hgs_forward_render(void* stream, int P, int W, int H, int R_capacity, int n_extra, int flags, const float* bg,
+                       const float* colors_precomp, const float* extra, void* geom_buf, void* binning_buf, void* image_buf,
+                       float* out_color) {
   hipStream_t s = (hipStream_t)stream;
   if (check_aligned(image_buf, "image_buf")) return 1;
   if (!bg || !out_color) { hgs_set_error("null bg/out_color"); return 1; }
   if (n_extra != 0 && n_extra != 4) { hgs_set_error("n_extra must be 0 or 4 (got %d)", n_extra); return 1; }
   if (n_extra && P > 0 && (!extra || ((size_t)extra & 15))) { hgs_set_error("extra colours must be a 16-byte aligned [P,4] array"); return 1; }
+  if ((flags & HGS_RECORDS_PACKED) && (flags & HGS_RECORDS_LAZY)) { hgs_set_error("HGS_RECORDS_PACKED and HGS_RECORDS_LAZY exclude each other"); return 1; }
   const int channels = 3 + n_extra;
   HgsImage im;
   hgs_image_carve((char*)image_buf, (size_t)W, (size_t)H, im, nullptr);
@@ -315,7 +307,7 @@ static int forward_render_impl(void* stream, int P, int W, int H, int R_capacity
       hgs_binning_carve((char*)binning_buf, (size_t)R_capacity, b, nullptr, channels);
       b.grec = g.grec;
       const long long tiles = (long long)((W + HGS_TILE - 1) / HGS_TILE) * ((H + HGS_TILE - 1) / HGS_TILE);
-      b.lazy = g_lazy_mode >= 0 ? g_lazy_mode : ((long long)R_capacity >= (long long)HGS_LAZY_MIN_MEAN_LIST * tiles ? 1 : 0);
+      b.lazy = (flags & HGS_RECORDS_LAZY) ? 1 : (flags & HGS_RECORDS_PACKED) ? 0 : ((long long)R_capacity >= (long long)HGS_LAZY_MIN_MEAN_LIST * tiles ? 1 : 0);
     }
     // the scatter also finishes the per-Gaussian instance offsets, so it runs even when nothing is visible
     const float* feat = colors_precomp ? colors_precomp : g.rgb;
@@ -326,44 +318,21 @@ static int forward_render_impl(void* stream, int P, int W, int H, int R_capacity
   return hgs_launch_blend_fwd(s, W, H, R_capacity > 0 ? R_capacity : 0, channels, bg, im, b, out_color);
 }
 
-int hgs_forward_render(void* stream, int P, int W, int H, int R_capacity, const float* bg, const float* colors_precomp,
-                       void* geom_buf, void* binning_buf, void* image_buf, float* out_color) {
-  return forward_render_impl(stream, P, W, H, R_capacity, bg, colors_precomp, nullptr, 0, geom_buf, binning_buf,
-                             image_buf, out_color);
-}
-
-int hgs_forward_render_multi(void* stream, int P, int W, int H, int R_capacity, const float* bg7,
-                             const float* colors_precomp, const float* extra4, void* geom_buf, void* binning_buf,
-                             void* image_buf, float* out_color7) {
-  return forward_render_impl(stream, P, W, H, R_capacity, bg7, colors_precomp, extra4, 4, geom_buf, binning_buf,
-                             image_buf, out_color7);
-}
-
-size_t hgs_binning_bytes_multi(int R) { HgsBinning b; return hgs_binning_carve(nullptr, (size_t)(R > 0 ? R : 0), b, nullptr, 7); }
-size_t hgs_backward_scratch_bytes_multi(int P, int R) {
-  // R instance rows of 16 floats, then (256-byte aligned) row_reduce_kernel's per-Gaussian sums and per-run partial sums
-  const size_t p = (size_t)(P > 0 ? P : 0), r = (size_t)(R > 0 ? R : 0);
-  return hgs_align_up(r * 16 * sizeof(float)) + hgs_align_up(hgs_row_reduce_floats(p, r) * sizeof(float)) + HGS_ALIGN;
-}
-// hgs_set_row_reduce: whether the 7-channel backward sums the instance rows per Gaussian with a launch of its own
-// (row_reduce_kernel, balanced by rows): 1 yes, 0 no, -1 (default) where the pass's R is at least HGS_RR_AUTO_RATIO x P
+// whether the 7-channel backward sums the instance rows per Gaussian with a launch of its own (row_reduce_kernel, balanced by
+// rows) when the caller has chosen neither HGS_ROWS_REDUCE nor HGS_ROWS_INLINE: where the pass's R is at least this many times P
 #define HGS_RR_AUTO_RATIO 8
-static int g_row_reduce_mode = -1;
-extern "C" int hgs_set_row_reduce(int mode) {
-  const int was = g_row_reduce_mode;
-  g_row_reduce_mode = mode > 0 ? 1 : (mode < 0 ? -1 : 0);
-  return was;
-}
 
-static int backward_impl(void* stream, int P, int D, int M, int R, int W, int H, const float* bg, const float* means3D,
-                         const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
-                         const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+static int backward_impl(void* stream, int P, int D, int M, int R, int W, int H, int n_extra, int flags, const float* bg,
+                         const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                         float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
                          const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
                          const void* geom_buf, const void* binning_buf, const void* image_buf,
-                         const float* const* dL_dpix_planes, void* scratch, int n_extra, float* dL_dextra, float* dL_dmeans2D, float* dL_dconic,
+                         const float* const* dL_dpix_planes, void* scratch, float* dL_dextra, float* dL_dmeans2D, float* dL_dconic,
                          float* dL_dopacity, float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                         float* dL_dscales, float* dL_drotations, const HgsParamBackward* pb = nullptr) {
+                         float* dL_dscales, float* dL_drotations, const HgsParamBackward* pb) {
   hipStream_t s = (hipStream_t)stream;
+  if (n_extra != 0 && n_extra != 4) { hgs_set_error("n_extra must be 0 or 4 (got %d)", n_extra); return 1; }
+  if ((flags & HGS_ROWS_INLINE) && (flags & HGS_ROWS_REDUCE)) { hgs_set_error("HGS_ROWS_INLINE and HGS_ROWS_REDUCE exclude each other"); return 1; }
   if (P == 0) return 0;  // rasterize_points.cu:161
   if (check_aligned(geom_buf, "geom_buf") || check_aligned(image_buf, "image_buf")) return 1;
   // (viewmatrix / projmatrix / campos are read at kernel entry whatever the colour source: required, include/hgs.h)
@@ -382,7 +351,8 @@ static int backward_impl(void* stream, int P, int D, int M, int R, int W, int H,
   float* inst_grad = nullptr;
   // many instances per Gaussian (the states the three-stage workflow lives in: a Stage-I cloud at 1080p, the merged strand
   // model): the per-Gaussian sums of the rows are taken by a launch that is balanced by rows (csrc/hgs_preprocess.hip)
-  const bool reduce_rows = n_extra && R > 0 && (g_row_reduce_mode > 0 || (g_row_reduce_mode < 0 && (long long)R >= (long long)HGS_RR_AUTO_RATIO * P));
+  const bool reduce_rows = n_extra && R > 0 &&
+                           ((flags & HGS_ROWS_REDUCE) || (!(flags & HGS_ROWS_INLINE) && (long long)R >= (long long)HGS_RR_AUTO_RATIO * P));
   if (R > 0) {
     if (check_aligned(binning_buf, "binning_buf") || check_aligned(scratch, "scratch")) return 1;
     hgs_binning_carve((char*)binning_buf, (size_t)R, b, nullptr, channels);
@@ -420,10 +390,10 @@ static int check_adam_inline(const HgsAdamInline& a, int n_slots, const char* wh
   }
   return 0;
 }
-int hgs_backward_multi_params(void* stream, int P, int D, int M, int R, int W, int H, const float* bg7, const float* means3D,
-                              const float* shs, const float* scales, const float* rotations, const float* viewmatrix,
-                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
-                              const void* geom_buf, const void* binning_buf, const void* image_buf,
+int hgs_backward_multi_params(void* stream, int P, int D, int M, int R, int W, int H, int flags, const float* bg7,
+                              const float* means3D, const float* shs, const float* scales, const float* rotations,
+                              const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                              float tan_fovy, const int* radii, const void* geom_buf, const void* binning_buf, const void* image_buf,
                               const float* const* dL_dpix_planes7, void* scratch, float* dL_dsh, const HgsParamBackward* pb) {
   if (!pb || (pb->kind != HGS_PARAMS_HAIR && pb->kind != HGS_PARAMS_CLOUD)) { hgs_set_error("hgs_backward_multi_params: params->kind must be HGS_PARAMS_HAIR or HGS_PARAMS_CLOUD"); return 1; }
   if (P == 0 && pb->head_tail.out) { hgs_set_error("hgs_backward_multi_params: a deferred loss-head tail needs a launch (P > 0)"); return 1; }
@@ -445,39 +415,22 @@ int hgs_backward_multi_params(void* stream, int P, int D, int M, int R, int W, i
   }
   if (check_adam_inline(pb->adam, pb->kind == HGS_PARAMS_HAIR ? 4 : 6, "hgs_backward_multi_params")) return 1;
   HgsParamBackward p = *pb;
-  return backward_impl(stream, P, D, M, R, W, H, bg7, means3D, shs, nullptr, scales, 1.f, rotations, nullptr, viewmatrix,
+  return backward_impl(stream, P, D, M, R, W, H, 4, flags, bg7, means3D, shs, nullptr, scales, 1.f, rotations, nullptr, viewmatrix,
                        projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buf, binning_buf, image_buf, dL_dpix_planes7, scratch,
-                       4, nullptr, p.dL_dmeans2D_rgb, nullptr, nullptr, nullptr, nullptr, nullptr, dL_dsh, nullptr, nullptr, &p);
+                       nullptr, p.dL_dmeans2D_rgb, nullptr, nullptr, nullptr, nullptr, nullptr, dL_dsh, nullptr, nullptr, &p);
 }
 
-int hgs_backward(void* stream, int P, int D, int M, int R, int W, int H, const float* bg, const float* means3D,
-                 const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
+int hgs_backward(void* stream, int P, int D, int M, int R, int W, int H, int n_extra, int flags, const float* bg,
+                 const float* means3D, const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
                  const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
                  const float* campos, float tan_fovx, float tan_fovy, const int* radii, const void* geom_buf,
-                 const void* binning_buf, const void* image_buf, const float* dL_dpix, void* scratch,
-                 float* dL_dmeans2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolors, float* dL_dmeans3D,
-                 float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations) {
-  if (!dL_dpix && P > 0) { hgs_set_error("null dL_dpix"); return 1; }
-  const size_t HW = (size_t)H * W;
-  const float* planes[3] = {dL_dpix, dL_dpix + HW, dL_dpix + 2 * HW};
-  return backward_impl(stream, P, D, M, R, W, H, bg, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
-                       cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buf, binning_buf,
-                       image_buf, planes, scratch, 0, nullptr, dL_dmeans2D, dL_dconic, dL_dopacity, dL_dcolors,
-                       dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations);
-}
-
-int hgs_backward_multi(void* stream, int P, int D, int M, int R, int W, int H, const float* bg7, const float* means3D,
-                       const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
-                       const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                       const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
-                       const void* geom_buf, const void* binning_buf, const void* image_buf,
-                       const float* const* dL_dpix_planes7, void* scratch, float* dL_dextra4, float* dL_dmeans2D_rgb, float* dL_dconic, float* dL_dopacity,
-                       float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
-                       float* dL_drotations) {
-  return backward_impl(stream, P, D, M, R, W, H, bg7, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
-                       cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buf, binning_buf,
-                       image_buf, dL_dpix_planes7, scratch, 4, dL_dextra4, dL_dmeans2D_rgb, dL_dconic, dL_dopacity, dL_dcolors,
-                       dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations);
+                 const void* binning_buf, const void* image_buf, const float* const* dL_dpix_planes, void* scratch,
+                 float* dL_dextra, float* dL_dmeans2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolors,
+                 float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations) {
+  return backward_impl(stream, P, D, M, R, W, H, n_extra, flags, bg, means3D, shs, colors_precomp, scales, scale_modifier,
+                       rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buf, binning_buf,
+                       image_buf, dL_dpix_planes, scratch, dL_dextra, dL_dmeans2D, dL_dconic, dL_dopacity, dL_dcolors,
+                       dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, nullptr);
 }
 
 int hgs_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

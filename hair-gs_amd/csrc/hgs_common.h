@@ -63,7 +63,7 @@ struct HgsBinning {
   const float4* grec;
   int lazy;
 };
-// Which passes are lazy (hgs_set_lazy_records(-1), the default): those whose capacity (or exact instance count) is at least this
+// Which passes are lazy (hgs_forward_render without HGS_RECORDS_*): those whose capacity (or exact instance count) is at least this
 // many entries per tile (at 64 the whole loop of tools/soak.py, whose model passes through 50-200, was 1 % slower than packed; at
 // 128 the strand workloads below config 5's size stay packed).  Two thirds of a dense Stage-I frame's records were written and
 // never read (they lie behind their tile's last contributor), and a long list hides the template gather behind the previous batch's arithmetic: config 4 +2.0 %,
@@ -305,7 +305,7 @@ struct HgsFwdArgs {
   const float *viewmatrix, *projmatrix, *campos;
   float scale_modifier, tan_fovx, tan_fovy;
   int prefiltered;
-  int tile_cull;       // shrink every tile rectangle to the alpha >= 1/255 ellipse's bounding box (hgs_set_tile_cull)
+  int tile_cull;       // shrink every tile rectangle to the alpha >= 1/255 ellipse's bounding box (HGS_TILE_CULL)
   int row_runs;        // HGS_COUNT_ROW_RUNS: large rectangles leave two marks per tile row in im.tile_delta; the pass's scan (scan_kernel, or
                        // the scan workgroups of scatter_kernel, told through bit 0 of the parked pointer) adds their running sum
   // != 0: no scan launch follows; the scatter kernel scans the tile counts itself (see scatter_kernel) and reports the

@@ -334,7 +334,9 @@ __device__ __forceinline__ void preprocess_fwd_body(const HgsFwdArgs& a, const H
         // tau = ln(255 opacity), whose bounding box has half extents sqrt(2 tau cov_xx), sqrt(2 tau cov_yy) (cov = Q^-1).
         // Tiles outside that box (inflated like the quadrant masks of the sort kernel: 0.05% + 0.01 px) hold no pixel
         // that passes the test: they get no instance.  For thin strand Gaussians that is a quarter of all instances;
-        // images and gradients are bit-identical with and without (tests/test_gpu_raster.py).
+        // image, radii and final_T are bit-identical with and without, the gradients too except where the backward streams
+        // or row_reduce_kernel sums a Gaussian's rows: the same terms, associated differently (include/hgs.h HGS_TILE_CULL,
+        // tests/test_gpu_raster.py::test_tile_cull_changes_no_output).
         const float tau = logf(255.f * conic_o.w);
         const float cdet = conic_o.x * conic_o.z - conic_o.y * conic_o.y;
         if (!(tau > 0.f)) {
@@ -1054,7 +1056,7 @@ __global__ __launch_bounds__(HGS_BLOCK) void row_reduce_kernel(const float4* __r
 // view-dependent SH code is compiled out (136 -> fewer registers for a kernel that lives on its occupancy).
 // MODE (round 5, the backward mirror of hair_preprocess_fwd_kernel / cloud_preprocess_fwd_kernel): the lane that has just
 // finished Gaussian k's gradients holds everything the parameters' backward needs of it in registers.
-//   MODE 0  the rasterizer's own outputs (nine gradient tensors, hgs_backward / hgs_backward_multi);
+//   MODE 0  the rasterizer's own outputs (the gradient tensors of hgs_backward);
 //   MODE 1  strand model (hgs_backward_multi_params, HGS_PARAMS_HAIR): the segment's geometry backward is applied HERE, once --
 //           two endpoint contributions (h - gD, h + gD; hgs_strand_bwd.h), d_width, d_opacity_raw, d_mask_raw, dL_dsh and the
 //           densification statistics leave the lane instead of 124 bytes of per-Gaussian gradients that strand_bwd_kernel's

@@ -2,6 +2,7 @@
 (submodules/diff-gaussian-rasterization/ext.cpp:15-19): same three functions, same argument order, same
 return tuples -- implemented over the C ABI of libhgs.so (include/hgs.h) with ctypes."""
 import ctypes as C
+import os
 
 import torch
 
@@ -18,6 +19,9 @@ import hgs_runtime as rt
 # rasterize_gaussians is then the capacity (it only sizes/carves buffers downstream).
 IMAGE_PREZEROED = 2   # include/hgs.h HGS_IMAGE_PREZEROED (flag in `prefiltered`)
 COUNT_ROW_RUNS = 4    # include/hgs.h HGS_COUNT_ROW_RUNS
+TILE_CULL = 8         # include/hgs.h HGS_TILE_CULL
+RECORDS_PACKED, RECORDS_LAZY = 16, 32   # include/hgs.h HGS_RECORDS_* (flags of hgs_forward_render)
+ROWS_INLINE, ROWS_REDUCE = 64, 128      # include/hgs.h HGS_ROWS_* (flags of hgs_backward)
 _state = {"last_R": 0, "last_counts_clean": False, "async": False, "cap": 0, "slack": 1.5, "dirty": False, "cap_used": None, "max_R": {}, "cull": None}
 
 
@@ -39,23 +43,30 @@ def bucket_capacity(n):
 
 
 def set_tile_cull(enabled=True):
-    """Tile culling (include/hgs.h hgs_set_tile_cull: drop the (Gaussian, tile) instances no pixel can blend; image,
-    radii and every gradient are bit-identical with and without) for ALL entry points of this module: True / False, or
-    None for the per-entry-point defaults:
+    """Tile culling (include/hgs.h HGS_TILE_CULL: drop the (Gaussian, tile) instances no pixel can blend) for ALL entry points
+    of this module: True / False, or None for the per-entry-point defaults:
       rasterize_gaussians         OFF -- the reference's own function: `num_rendered`, the tile lists in the returned
                                   buffers and `n_contrib` are the reference's, entry for entry;
       rasterize_gaussians_culled  (what diff_gaussian_rasterization.GaussianRasterizer, i.e. render(), calls) and
       rasterize_gaussians_multi   ON -- callers that only see the image, the radii and the gradients.
-    Returns the previous setting."""
+    Image, radii and final_T are bit-identical with and without; so are the gradients, except those of Gaussians whose rows the
+    backward streams or row_reduce_kernel sums (the same terms, associated differently).  Tiles long enough to be blended in
+    segments agree to rounding.  Returns the previous setting."""
     was = _state["cull"]
     _state["cull"] = None if enabled is None else bool(enabled)
     return was
 
 
+def _pinned(mode, env):
+    """`mode`, unless the A/B aid `env` (HGS_ROW_REDUCE, HGS_ROW_RUNS, HGS_LAZY_RECORDS) = 0 / 1 pins it for the whole process."""
+    v = os.environ.get(env)
+    return v == "1" if v in ("0", "1") else mode
+
+
 def set_row_reduce(mode):
-    """How the single-pass backward sums the instance rows per Gaussian (include/hgs.h hgs_set_row_reduce): True / False, or
-    None = decide per call -- from the exact instance count of a blocking-mode pass (R >= 4 P), from the library's capacity rule
-    otherwise.  train.GraphedStep.capture() sets it from the instance counts its warm-up passes measured, so that the form
+    """How the single-pass backward sums the instance rows per Gaussian (include/hgs.h HGS_ROWS_REDUCE / HGS_ROWS_INLINE): True /
+    False, or None = decide per call -- from the exact instance count of a blocking-mode pass (R >= 4 P), from the library's
+    capacity rule otherwise.  train.GraphedStep.capture() sets it from the instance counts its warm-up passes measured, so that the form
     follows the MODEL (and with it every replay and every eager iteration until the next capture), not the capacity a run
     happens to hold: a run that rolls back and raises its capacity keeps the arithmetic of one that never overflowed."""
     was = _state.get("row_reduce")
@@ -63,16 +74,26 @@ def set_row_reduce(mode):
     return was
 
 
-def _apply_row_reduce(L, P, R):
-    import os
-    env = os.environ.get("HGS_ROW_REDUCE")          # A/B aid: 0 / 1 pins the form for the whole process
-    if env in ("0", "1"):
-        L.hgs_set_row_reduce(int(env))
-        return
-    mode = _state.get("row_reduce")
-    if mode is None:
-        mode = (1 if R >= 4 * P else 0) if not _state["async"] else -1
-    L.hgs_set_row_reduce(int(mode))
+def _row_reduce_flags(P, R):
+    mode = _pinned(_state.get("row_reduce"), "HGS_ROW_REDUCE")
+    if mode is None and not _state["async"]:
+        mode = R >= 4 * P
+    return 0 if mode is None else (ROWS_REDUCE if mode else ROWS_INLINE)   # (None: the library's rule, R >= 8 P)
+
+
+def set_lazy_records(mode):
+    """How the blend kernels of the following passes (and of their backwards) get the per-entry records (include/hgs.h
+    HGS_RECORDS_LAZY / HGS_RECORDS_PACKED): True = built from the Gaussians' templates through the sorted keys, False = packed
+    by the sort kernel, None = the library's rule (lazy from 128 entries per tile).  Images and gradients are the same bits
+    either way.  Returns the previous setting."""
+    was = _state.get("lazy_records")
+    _state["lazy_records"] = None if mode is None else bool(mode)
+    return was
+
+
+def _records_flags():
+    lazy = _pinned(_state.get("lazy_records"), "HGS_LAZY_RECORDS")
+    return 0 if lazy is None else (RECORDS_LAZY if lazy else RECORDS_PACKED)   # (None: the library's rule)
 
 
 def set_row_runs(mode):
@@ -85,11 +106,7 @@ def set_row_runs(mode):
 
 
 def _row_runs_flag(P, use_async):
-    import os
-    env = os.environ.get("HGS_ROW_RUNS")            # A/B aid: 0 / 1 pins the form for the whole process
-    mode = _state.get("row_runs")
-    if env in ("0", "1"):
-        mode = env == "1"
+    mode = _pinned(_state.get("row_runs"), "HGS_ROW_RUNS")
     if mode is None:
         mode = (_state["cap"] if use_async else _state.get("last_exact_R", 0)) >= 8 * P
     return COUNT_ROW_RUNS if (mode and P > 0) else 0
@@ -151,8 +168,8 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 def rasterize_gaussians_culled(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                                viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                                prefiltered, debug):
-    """rasterize_gaussians with tile culling on (this module's extension; what GaussianRasterizer / render() call): same
-    image, radii and gradients bit for bit, fewer instances in the buffers."""
+    """rasterize_gaussians with tile culling on (this module's extension; what GaussianRasterizer / render() call): fewer
+    instances in the buffers; the same image, radii and final_T bit for bit, and gradients as set_tile_cull states."""
     return _forward(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                     projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug,
                     None, True)
@@ -161,7 +178,7 @@ def rasterize_gaussians_culled(background, means3D, colors, opacity, scales, rot
 def rasterize_gaussians_multi(background7, means3D, colors, extra4, opacity, scales, rotations, scale_modifier,
                               cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
                               degree, campos, prefiltered, debug, image_buffer=None, hair=None):
-    """Single-pass 7-channel forward (hgs_forward_render_multi): RGB + `extra4` [P,4] unclamped channels blended with
+    """Single-pass 7-channel forward (hgs_forward_render, n_extra 4): RGB + `extra4` [P,4] unclamped channels blended with
     the same weights.  Returns (num_rendered, out_color[7,H,W], radii, geomBuffer, binningBuffer, imgBuffer).
     image_buffer: a uint8 tensor of hgs_image_bytes(W, H) whose counters the caller has cleared on this stream
     (hgs_iteration_prologue): used as the imgBuffer, and the pass skips its own clearing launch."""
@@ -198,7 +215,6 @@ class CloudSource:
 def will_fuse_hair(W, H):
     """Would a pass with a HairSource at this size run the one-launch form now?  (capacity mode with a learnt capacity,
     at most HGS_FUSED_PREPROCESS_MAX_TILES tiles)"""
-    import os
     return (_state["async"] and _state["cap"] > 0 and os.environ.get("HGS_FUSE_PREPROCESS", "1") != "0"
             and ((int(W) + 15) // 16) * ((int(H) + 15) // 16) <= rt.FUSED_PREPROCESS_MAX_TILES)
 
@@ -220,7 +236,6 @@ def _forward(background, means3D, colors, opacity, scales, rotations, scale_modi
     if means3D.ndim != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:57-59
     L = rt.lib()
-    L.hgs_set_tile_cull(int(_state["cull"] if _state["cull"] is not None else bool(cull)))   # host-side switch, read by this pass
     means3D = rt.require_gpu_tensor(means3D, "means3D", torch.float32)
     dev = means3D.device
     P, H, W = means3D.shape[0], int(image_height), int(image_width)
@@ -231,7 +246,8 @@ def _forward(background, means3D, colors, opacity, scales, rotations, scale_modi
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
     u8 = dict(dtype=torch.uint8, device=dev)
     geom = torch.empty((L.hgs_geom_bytes(P),), **u8)
-    flags = int(bool(prefiltered))
+    cull = _state["cull"] if _state["cull"] is not None else cull
+    flags = int(bool(prefiltered)) | (TILE_CULL if cull else 0)
     if image_buffer is not None:
         if image_buffer.numel() != L.hgs_image_bytes(W, H) or image_buffer.dtype != torch.uint8 or image_buffer.device != dev:
             raise RuntimeError("image_buffer: need a uint8 tensor of hgs_image_bytes(W, H) on the inputs' device")
@@ -301,14 +317,9 @@ def _forward(background, means3D, colors, opacity, scales, rotations, scale_modi
             _state["last_exact_R"] = R
             if _state["async"]:  # first call: learn the scale of the scene with one blocking read
                 _state["cap"] = max(_state["cap"], bucket_capacity(int(R * _state["slack"]) + 4096))
-        if extra_ is None:
-            binning = torch.empty((L.hgs_binning_bytes(R),), **u8)
-            rt.check(L.hgs_forward_render(stream, P, W, H, R, rt.ptr(bg), rt.ptr(colors_), rt.ptr(geom), rt.ptr(binning),
-                                          rt.ptr(img), rt.ptr(out_color)))
-        else:
-            binning = torch.empty((L.hgs_binning_bytes_multi(R),), **u8)
-            rt.check(L.hgs_forward_render_multi(stream, P, W, H, R, rt.ptr(bg), rt.ptr(colors_), rt.ptr(extra_),
-                                                rt.ptr(geom), rt.ptr(binning), rt.ptr(img), rt.ptr(out_color)))
+        binning = torch.empty((L.hgs_binning_bytes(R, n_ch),), **u8)
+        rt.check(L.hgs_forward_render(stream, P, W, H, R, n_ch - 3, _records_flags(), rt.ptr(bg), rt.ptr(colors_),
+                                      rt.ptr(extra_), rt.ptr(geom), rt.ptr(binning), rt.ptr(img), rt.ptr(out_color)))
         if use_async and max_rendered is None:
             _state["dirty"] = True
             _state["cap_used"] = R if _state["cap_used"] is None else min(_state["cap_used"], R)
@@ -321,11 +332,61 @@ def _forward(background, means3D, colors, opacity, scales, rotations, scale_modi
 def _scratch(nbytes, dev):
     """Backward scratch (per-instance partial-gradient rows).  It is deliberately NOT cleared by the library; with
     HGS_POISON_SCRATCH=1 (tests) it is filled with NaN so that any read of a row nobody wrote shows up."""
-    import os
     buf = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     if os.environ.get("HGS_POISON_SCRATCH") == "1" and nbytes >= 4:
         buf[:nbytes // 4 * 4].view(torch.float32).fill_(float("nan"))
     return buf
+
+
+def _backward(n_extra, background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+              projmatrix, tan_fovx, tan_fovy, planes, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug=False,
+              params=None):
+    """hgs_backward of a pass with 3 + n_extra channels (`planes`: one [H,W] gradient tensor per channel), or with `params`
+    hgs_backward_multi_params.  Returns the gradients in hgs_backward's order -- dL_dextra (None for 3 channels), dL_dmeans2D,
+    dL_dconic, dL_dopacity, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations --, or dL_dsh alone with
+    `params`."""
+    L = rt.lib()
+    means3D = rt.require_gpu_tensor(means3D, "means3D", torch.float32)
+    dev, P = means3D.device, means3D.shape[0]
+    H, W = int(planes[0].shape[-2]), int(planes[0].shape[-1])
+    M = sh.shape[1] if (params is not None or (sh is not None and sh.numel() != 0)) else 0   # (the parameter form has SH colours)
+    f32 = dict(dtype=torch.float32, device=dev)
+    new = torch.empty if P > 0 else torch.zeros  # the kernel writes every element when P > 0
+    if params is None:
+        grads = [new((P, 4), **f32) if n_extra else None, new((P, 3), **f32), new((P, 2, 2), **f32), new((P, 1), **f32),
+                 new((P, 3), **f32), new((P, 3), **f32), new((P, 6), **f32), new((P, M, 3), **f32), new((P, 3), **f32),
+                 new((P, 4), **f32)]
+        if P == 0:
+            return grads
+    else:
+        grads = new((P, M, 3), **f32)
+    scratch = _scratch(L.hgs_backward_scratch_bytes(P, int(R), 3 + n_extra), dev)
+    # keep every (possibly freshly made contiguous) input alive in a local until the launch has been enqueued:
+    # a temporary released early would hand its block to the next temporary of the same size
+    planes = [rt.require_gpu_tensor(g, "dL_dpix plane", torch.float32) for g in planes]
+    plane_ptrs = (C.c_void_p * (3 + n_extra))(*[g.data_ptr() for g in planes])
+    bg_, sh_, colors_, scales_, rots_, cov_ = (_f32(background, "bg"), _f32(sh, "sh"), _f32(colors, "colors_precomp"),
+                                               _f32(scales, "scales"), _f32(rotations, "rotations"),
+                                               _f32(cov3D_precomp, "cov3D_precomp"))
+    view_, proj_, cam_ = _f32(viewmatrix, "viewmatrix"), _f32(projmatrix, "projmatrix"), _f32(campos, "campos")
+    radii_ = rt.require_gpu_tensor(radii, "radii", torch.int32)
+    flags = _row_reduce_flags(P, int(R))
+    with torch.cuda.device(dev):
+        if params is None:
+            rt.check(L.hgs_backward(rt.current_stream(), P, int(degree), M, int(R), W, H, n_extra, flags, rt.ptr(bg_),
+                                    rt.ptr(means3D), rt.ptr(sh_), rt.ptr(colors_), rt.ptr(scales_), float(scale_modifier),
+                                    rt.ptr(rots_), rt.ptr(cov_), rt.ptr(view_), rt.ptr(proj_), rt.ptr(cam_), float(tan_fovx),
+                                    float(tan_fovy), rt.ptr(radii_), rt.ptr(geomBuffer), rt.ptr(binningBuffer),
+                                    rt.ptr(imageBuffer), plane_ptrs, rt.ptr(scratch), *[rt.ptr(g) for g in grads]))
+        else:
+            rt.check(L.hgs_backward_multi_params(rt.current_stream(), P, int(degree), M, int(R), W, H, flags, rt.ptr(bg_),
+                                                 rt.ptr(means3D), rt.ptr(sh_), rt.ptr(scales_), rt.ptr(rots_), rt.ptr(view_),
+                                                 rt.ptr(proj_), rt.ptr(cam_), float(tan_fovx), float(tan_fovy), rt.ptr(radii_),
+                                                 rt.ptr(geomBuffer), rt.ptr(binningBuffer), rt.ptr(imageBuffer), plane_ptrs,
+                                                 rt.ptr(scratch), rt.ptr(grads), C.byref(params)))
+        if debug:
+            torch.cuda.synchronize(dev)
+    return grads
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
@@ -333,83 +394,24 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  geomBuffer, R, binningBuffer, imageBuffer, debug):
     """RasterizeGaussiansBackwardCUDA (rasterize_points.cu:117-196).
     Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)."""
-    L = rt.lib()
-    means3D = rt.require_gpu_tensor(means3D, "means3D", torch.float32)
-    dev = means3D.device
-    P = means3D.shape[0]
-    H, W = int(dL_dout_color.shape[1]), int(dL_dout_color.shape[2])
-    M = sh.shape[1] if (sh is not None and sh.numel() != 0) else 0
-    f32 = dict(dtype=torch.float32, device=dev)
-    new = torch.empty if P > 0 else torch.zeros  # the kernel writes every element when P > 0
-    dL_dmeans3D, dL_dmeans2D, dL_dcolors = new((P, 3), **f32), new((P, 3), **f32), new((P, 3), **f32)
-    dL_dconic, dL_dopacity, dL_dcov3D = new((P, 2, 2), **f32), new((P, 1), **f32), new((P, 6), **f32)
-    dL_dsh, dL_dscales, dL_drotations = new((P, M, 3), **f32), new((P, 3), **f32), new((P, 4), **f32)
-    if P == 0:
-        return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
-    scratch = _scratch(L.hgs_backward_scratch_bytes(P, int(R)), dev)
-    # keep every (possibly freshly made contiguous) input alive in a local until the launch has been enqueued:
-    # a temporary released early would hand its block to the next temporary of the same size
-    dpix = rt.require_gpu_tensor(dL_dout_color, "dL_dout_color", torch.float32)
-    bg_, sh_, colors_, scales_, rots_, cov_ = (_f32(background, "bg"), _f32(sh, "sh"), _f32(colors, "colors_precomp"),
-                                               _f32(scales, "scales"), _f32(rotations, "rotations"),
-                                               _f32(cov3D_precomp, "cov3D_precomp"))
-    view_, proj_, cam_ = _f32(viewmatrix, "viewmatrix"), _f32(projmatrix, "projmatrix"), _f32(campos, "campos")
-    radii_ = rt.require_gpu_tensor(radii, "radii", torch.int32)
-    with torch.cuda.device(dev):
-        rt.check(L.hgs_backward(rt.current_stream(), P, int(degree), M, int(R), W, H, rt.ptr(bg_), rt.ptr(means3D),
-                                rt.ptr(sh_), rt.ptr(colors_), rt.ptr(scales_), float(scale_modifier), rt.ptr(rots_),
-                                rt.ptr(cov_), rt.ptr(view_), rt.ptr(proj_), rt.ptr(cam_), float(tan_fovx), float(tan_fovy),
-                                rt.ptr(radii_), rt.ptr(geomBuffer), rt.ptr(binningBuffer), rt.ptr(imageBuffer),
-                                rt.ptr(dpix), rt.ptr(scratch), rt.ptr(dL_dmeans2D), rt.ptr(dL_dconic), rt.ptr(dL_dopacity),
-                                rt.ptr(dL_dcolors), rt.ptr(dL_dmeans3D), rt.ptr(dL_dcov3D), rt.ptr(dL_dsh),
-                                rt.ptr(dL_dscales), rt.ptr(dL_drotations)))
-        if debug:
-            torch.cuda.synchronize(dev)
-    rasterize_gaussians_backward.last_dL_dconic = dL_dconic  # kept for the parity tests
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+    _, dmeans2D, dconic, dopacity, dcolors, dmeans3D, dcov3D, dsh, dscales, drotations = _backward(
+        0, background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+        tan_fovx, tan_fovy, dL_dout_color.unbind(0), sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug)
+    rasterize_gaussians_backward.last_dL_dconic = dconic  # kept for the parity tests
+    return dmeans2D, dcolors, dopacity, dmeans3D, dcov3D, dsh, dscales, drotations
 
 
 def rasterize_gaussians_multi_backward(background7, means3D, radii, colors, scales, rotations, scale_modifier,
                                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, grad_planes, sh,
                                        degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug):
-    """Backward of the single-pass mode (hgs_backward_multi).  `grad_planes`: list of 7 contiguous [H,W] tensors (views
+    """Backward of the single-pass mode (hgs_backward, n_extra 4).  `grad_planes`: list of 7 contiguous [H,W] tensors (views
     into larger gradient tensors are fine).  `background7=None` declares an all-zero background (include/hgs.h: selects the
     black-background specialisation of the blend backward; same gradients).  Returns (dL_dmeans2D_rgb, dL_dcolors, dL_dextra4, dL_dopacity,
     dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)."""
-    L = rt.lib()
-    means3D = rt.require_gpu_tensor(means3D, "means3D", torch.float32)
-    dev, P = means3D.device, means3D.shape[0]
-    H, W = int(grad_planes[0].shape[-2]), int(grad_planes[0].shape[-1])
-    M = sh.shape[1] if (sh is not None and sh.numel() != 0) else 0
-    f32 = dict(dtype=torch.float32, device=dev)
-    new = torch.empty if P > 0 else torch.zeros
-    dL_dmeans3D, dL_dmeans2D, dL_dcolors = new((P, 3), **f32), new((P, 3), **f32), new((P, 3), **f32)
-    dL_dconic, dL_dopacity, dL_dcov3D = new((P, 2, 2), **f32), new((P, 1), **f32), new((P, 6), **f32)
-    dL_dsh, dL_dscales, dL_drotations = new((P, M, 3), **f32), new((P, 3), **f32), new((P, 4), **f32)
-    dL_dextra = new((P, 4), **f32)
-    if P == 0:
-        return dL_dmeans2D, dL_dcolors, dL_dextra, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
-    scratch = _scratch(L.hgs_backward_scratch_bytes_multi(P, int(R)), dev)
-    planes = [rt.require_gpu_tensor(g, "grad plane", torch.float32) for g in grad_planes]
-    plane_ptrs = (C.c_void_p * 7)(*[g.data_ptr() for g in planes])
-    bg_, sh_, colors_, scales_, rots_, cov_ = (_f32(background7, "bg"), _f32(sh, "sh"), _f32(colors, "colors_precomp"),
-                                               _f32(scales, "scales"), _f32(rotations, "rotations"),
-                                               _f32(cov3D_precomp, "cov3D_precomp"))
-    view_, proj_, cam_ = _f32(viewmatrix, "viewmatrix"), _f32(projmatrix, "projmatrix"), _f32(campos, "campos")
-    radii_ = rt.require_gpu_tensor(radii, "radii", torch.int32)
-    _apply_row_reduce(L, P, int(R))
-    with torch.cuda.device(dev):
-        rt.check(L.hgs_backward_multi(rt.current_stream(), P, int(degree), M, int(R), W, H, rt.ptr(bg_), rt.ptr(means3D),
-                                      rt.ptr(sh_), rt.ptr(colors_), rt.ptr(scales_), float(scale_modifier), rt.ptr(rots_),
-                                      rt.ptr(cov_), rt.ptr(view_), rt.ptr(proj_), rt.ptr(cam_), float(tan_fovx),
-                                      float(tan_fovy), rt.ptr(radii_), rt.ptr(geomBuffer), rt.ptr(binningBuffer),
-                                      rt.ptr(imageBuffer), plane_ptrs, rt.ptr(scratch), rt.ptr(dL_dextra),
-                                      rt.ptr(dL_dmeans2D), rt.ptr(dL_dconic), rt.ptr(dL_dopacity), rt.ptr(dL_dcolors),
-                                      rt.ptr(dL_dmeans3D), rt.ptr(dL_dcov3D), rt.ptr(dL_dsh), rt.ptr(dL_dscales),
-                                      rt.ptr(dL_drotations)))
-        if debug:
-            torch.cuda.synchronize(dev)
-    return dL_dmeans2D, dL_dcolors, dL_dextra, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+    dextra, dmeans2D, _, dopacity, dcolors, dmeans3D, dcov3D, dsh, dscales, drotations = _backward(
+        4, background7, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+        tan_fovx, tan_fovy, grad_planes, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug)
+    return dmeans2D, dcolors, dextra, dopacity, dmeans3D, dcov3D, dsh, dscales, drotations
 
 
 def rasterize_gaussians_multi_backward_params(background7, means3D, radii, scales, rotations, viewmatrix, projmatrix, tan_fovx,
@@ -417,26 +419,8 @@ def rasterize_gaussians_multi_backward_params(background7, means3D, radii, scale
                                               imageBuffer, params):
     """hgs_backward_multi_params: the single-pass backward whose per-Gaussian launch also applies the parameters' backward
     (`params`: a filled hgs_runtime.ParamBackward; its output tensors are the caller's).  Returns dL_dsh [P,M,3]."""
-    L = rt.lib()
-    means3D = rt.require_gpu_tensor(means3D, "means3D", torch.float32)
-    dev, P = means3D.device, means3D.shape[0]
-    H, W = int(grad_planes[0].shape[-2]), int(grad_planes[0].shape[-1])
-    M = sh.shape[1]
-    dL_dsh = (torch.empty if P > 0 else torch.zeros)((P, M, 3), dtype=torch.float32, device=dev)
-    scratch = _scratch(L.hgs_backward_scratch_bytes_multi(P, int(R)), dev)
-    planes = [rt.require_gpu_tensor(g, "grad plane", torch.float32) for g in grad_planes]
-    plane_ptrs = (C.c_void_p * 7)(*[g.data_ptr() for g in planes])
-    bg_, sh_, scales_, rots_ = _f32(background7, "bg"), _f32(sh, "sh"), _f32(scales, "scales"), _f32(rotations, "rotations")
-    view_, proj_, cam_ = _f32(viewmatrix, "viewmatrix"), _f32(projmatrix, "projmatrix"), _f32(campos, "campos")
-    radii_ = rt.require_gpu_tensor(radii, "radii", torch.int32)
-    _apply_row_reduce(L, P, int(R))
-    with torch.cuda.device(dev):
-        rt.check(L.hgs_backward_multi_params(rt.current_stream(), P, int(degree), M, int(R), W, H, rt.ptr(bg_), rt.ptr(means3D),
-                                             rt.ptr(sh_), rt.ptr(scales_), rt.ptr(rots_), rt.ptr(view_), rt.ptr(proj_), rt.ptr(cam_),
-                                             float(tan_fovx), float(tan_fovy), rt.ptr(radii_), rt.ptr(geomBuffer),
-                                             rt.ptr(binningBuffer), rt.ptr(imageBuffer), plane_ptrs, rt.ptr(scratch),
-                                             rt.ptr(dL_dsh), C.byref(params)))
-    return dL_dsh
+    return _backward(4, background7, means3D, radii, None, scales, rotations, 1.0, None, viewmatrix, projmatrix, tan_fovx,
+                     tan_fovy, grad_planes, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, params=params)
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):

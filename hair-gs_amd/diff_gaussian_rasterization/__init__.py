@@ -90,7 +90,7 @@ class _RasterizeGaussiansMulti(torch.autograd.Function):
     buffer, so the losses' gradients arrive as separate tensors and are handed to the kernel plane by plane (no
     zero-filled 7-channel gradient is ever assembled).  means2D's gradient is the RGB channels' screen-space gradient.
     `black_background=True` is the CALLER's statement that raster_settings.bg is all zero: the backward then runs the
-    black-background specialisation (include/hgs.h hgs_backward_multi, bg == NULL); nothing here inspects the tensor."""
+    black-background specialisation (include/hgs.h hgs_backward, bg == NULL); nothing here inspects the tensor."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, extra4, opacities, scales, rotations, cov3Ds_precomp,

@@ -21,21 +21,16 @@ SIGNATURES = {
     "hgs_last_error": (C.c_char_p, []),
     "hgs_geom_bytes": (sz, [ci]),
     "hgs_image_bytes": (sz, [ci, ci]),
-    "hgs_binning_bytes": (sz, [ci]),
-    "hgs_backward_scratch_bytes": (sz, [ci, ci]),
+    "hgs_binning_bytes": (sz, [ci, ci]),
+    "hgs_backward_scratch_bytes": (sz, [ci, ci, ci]),
     "hgs_forward_preprocess": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, ci,
                                     vp, vp, vp, vp, vp]),
-    "hgs_forward_render": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
-    "hgs_backward": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp,
-                          vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "hgs_binning_bytes_multi": (sz, [ci]),
-    "hgs_backward_scratch_bytes_multi": (sz, [ci, ci]),
-    "hgs_forward_render_multi": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
-    "hgs_backward_multi": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp,
-                                vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "hgs_forward_render": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
+    "hgs_backward": (ci, [vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp,
+                          vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "hgs_param_backward_bytes": (sz, []),
-    "hgs_backward_multi_params": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, vp,
-                                       vp, vp]),
+    "hgs_backward_multi_params": (ci, [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp,
+                                       vp, vp, vp]),
     "hgs_hair_endpoint_gather": (ci, [vp, ci, vp, vp, vp, vp, vp]),
     "hgs_mark_visible": (ci, [vp, ci, vp, vp, vp, vp]),
     "hgs_dist2_scratch_bytes": (sz, [ci]),
@@ -102,10 +97,7 @@ SIGNATURES = {
     "hgs_raster_count": (ci, [vp, ci, ci, ci, ci, vp, C.c_longlong, vp, ci, vp, vp, vp]),
     "hgs_raster_fill": (ci, [vp, ci, ci, ci, ci, vp, C.c_longlong, vp, ci, vp, vp, vp, vp, vp]),
     "hgs_raster_resolve": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "hgs_set_tile_cull": (ci, [ci]),
     "hgs_set_segment_policy": (ci, [ci, ci, ci]),
-    "hgs_set_row_reduce": (ci, [ci]),
-    "hgs_set_lazy_records": (ci, [ci]),
     "hgs_debug_set_wg_trace": (ci, [vp, vp]),
     "hgs_prof_enable": (ci, [ci]),
     "hgs_prof_bracket_overhead_ms": (C.c_double, []),
@@ -200,7 +192,7 @@ HEAD_OUT = ["total", "l1", "dssim", "mask", "orientation", "smooth", "ori_count"
             "g_ori", "g_smooth", "total_fwd"]
 HEAD_NOUT = 16
 FUSED_PREPROCESS_MAX_TILES = 8192   # include/hgs.h HGS_FUSED_PREPROCESS_MAX_TILES
-ABI_VERSION = 8   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
+ABI_VERSION = 9   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
 
 
 def build(verbose=False):
@@ -237,8 +229,6 @@ def lib():
             if getattr(L, fn)() != C.sizeof(st):
                 raise HgsError(f"{LIB_PATH}: {fn}() = {getattr(L, fn)()} but the binding's struct has {C.sizeof(st)} bytes: "
                                "rebuild with hgs_runtime.build()")
-        if os.environ.get("HGS_LAZY_RECORDS") in ("0", "1"):      # A/B aid: pins include/hgs.h hgs_set_lazy_records for the process
-            L.hgs_set_lazy_records(int(os.environ["HGS_LAZY_RECORDS"]))
         _lib = L
     return _lib
 

@@ -1,5 +1,5 @@
 """The strand-Gaussian training iteration as ONE autograd node over the C ABI (include/hgs.h: hgs_select_view,
-hgs_hair_params_*, hgs_forward_render_multi / hgs_backward_multi, hgs_loss_head_*, hgs_densify_stats).
+hgs_hair_params_*, hgs_forward_render / hgs_backward with 7 channels, hgs_loss_head_*, hgs_densify_stats).
 
 What the reference does between `gaussians` and `loss.backward()` in train.py:135-171 for a HairGaussianModel --
 getters (scene/hair_gaussian_model.py:134-201), three render() calls, loss_function (loss/losses.py:319-355) and the
@@ -551,7 +551,7 @@ class FusedStrandStep:
         dev = self.views.device
         self.bg7 = torch.cat([bg.to(dev, torch.float32), torch.zeros(4, device=dev)]).contiguous()
         # a black background (the training default, train.py:94) is handed to the backward as NULL: its terms are compiled
-        # out of the blend backward (include/hgs.h hgs_backward_multi); one read-back here, at construction
+        # out of the blend backward (include/hgs.h hgs_backward); one read-back here, at construction
         self.bg7_backward = None if (bool((self.bg7 == 0).all()) and os.environ.get("HGS_BLACK_BG", "1") != "0") else self.bg7
         self.empty = torch.empty(0, device=dev)
         self.one = torch.ones((), dtype=torch.float32, device=dev)   # d loss / d loss, passed to backward(): no fill launch

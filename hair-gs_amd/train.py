@@ -533,7 +533,7 @@ class GraphedStep:
                 except raster.HgsCapacityOverflow:
                     pass
                 warm_R = max(warm_R, int(raster._state.get("last_exact_R", 0)) & 0x7FFFFFFF)
-        # how the single-pass backward sums its instance rows (include/hgs.h hgs_set_row_reduce) follows the MODEL: the instance
+        # how the single-pass backward sums its instance rows (include/hgs.h HGS_ROWS_REDUCE) follows the MODEL: the instance
         # counts the warm-up has just measured, not the capacity -- for this capture, its replays and the eager iterations until
         # the next capture (every rank sees the same model and the same warm-up views)
         raster.set_row_reduce(warm_R >= 4 * int(g.get_xyz.shape[0]))

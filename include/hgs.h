@@ -46,19 +46,22 @@ extern "C" {
  * 5, round 5: hgs_backward_multi_params / hgs_hair_endpoint_gather, HgsPrologue.adam_prep and the in-lane Adam update, and the contract that HgsHeadParams.tile_used also limits
  * what hgs_loss_head_forward writes of d_extra_unit -- a caller of version 4 that read those planes everywhere must not;
  * 6, round 6: tile_delta in the image buffer; 7: every image-buffer field behind tile_cursor starts on a 256-byte boundary, and a
- * misaligned HgsHeadParams.tile_used is an error of hgs_loss_head_forward; 8: hgs_strand_grow_plan / hgs_strand_grow_fill);
+ * misaligned HgsHeadParams.tile_used is an error of hgs_loss_head_forward; 8: hgs_strand_grow_plan / hgs_strand_grow_fill;
+ * 9: tile culling, the record form and the row sums are flag bits of each call instead of process-wide setters, and one render,
+ * backward and size function each serves 3 and 7 channels);
  * the Python binding refuses a library whose version or struct sizes differ from its own */
-#define HGS_ABI_VERSION 8
+#define HGS_ABI_VERSION 9
 #define HGS_TILE 16 /* cuda_rasterizer/config.h:16-17 */
 
 int hgs_abi_version(void);
 const char* hgs_last_error(void);
 
-/* ---- workspace sizes (bytes).  Layout is private; hgs_*_layout() exposes it for tests. ---- */
+/* ---- workspace sizes (bytes).  Layout is private; hgs_*_layout() exposes it for tests.  `channels`: 3, or 7 for the
+ * single-pass mode (n_extra = 4, hgs_forward_render); any other value gives 0. ---- */
 size_t hgs_geom_bytes(int P);
 size_t hgs_image_bytes(int W, int H);
-size_t hgs_binning_bytes(int R);
-size_t hgs_backward_scratch_bytes(int P, int R);
+size_t hgs_binning_bytes(int R, int channels);
+size_t hgs_backward_scratch_bytes(int P, int R, int channels);
 
 /* Forward, part 1: per-Gaussian preprocess (cull, cov3D, EWA cov2D, conic, radius, tile rect, SH->RGB)
  * + per-tile instance counts + scans.  Writes radii[P].  If num_rendered_host != NULL the call blocks
@@ -74,9 +77,21 @@ size_t hgs_backward_scratch_bytes(int P, int R);
  * clearing launch is skipped; bit 2 (HGS_COUNT_ROW_RUNS) = count the tile rectangles of more than 16 tiles by their tile
  * ROWS (two marks per row, which the pass's scan turns into counts) instead of tile by tile: the same counts; pays
  * where Gaussians cover many tiles each (a Stage-I cloud at 1080p, a merged strand
- * model: callers set it from the instances per Gaussian they have seen -- diff_gaussian_rasterization/_C.py). */
+ * model: callers set it from the instances per Gaussian they have seen -- diff_gaussian_rasterization/_C.py); bit 3
+ * (HGS_TILE_CULL) = tile culling, below. */
 #define HGS_IMAGE_PREZEROED 2
 #define HGS_COUNT_ROW_RUNS 4
+/* Tile culling.  The reference gives every Gaussian the tiles of its 3-sigma square (forward.cu:229-235, auxiliary.h:46-56)
+ * although a pixel only blends it where opacity * exp(power) >= 1/255 (forward.cu:358): with HGS_TILE_CULL the preprocess keeps
+ * only the tiles that the bounding box of that ellipse reaches, so num_rendered, the tile lists and n_contrib count fewer
+ * entries than the reference's -- the dropped ones are skipped by every pixel there too.  out_color, radii and final_T are
+ * bit-identical with and without; so are the gradients, except those of Gaussians whose wavefront of the per-Gaussian backward
+ * streams its rows (one of its 64 Gaussians has more than 32 instances) or whose rows row_reduce_kernel sums (HGS_ROWS_REDUCE):
+ * there the terms are the same, associated differently.  (Tiles whose list is long enough to be blended in segments,
+ * hgs_set_segment_policy, associate their transmittance products per segment: there image and gradients agree to rounding.)
+ * Without the bit the lists are the reference's exactly (the parity tests of the binning stages use that).  The backward
+ * takes no such bit: the buffers carry the rectangles. */
+#define HGS_TILE_CULL 8
 /* Value a max_rendered word takes when a workgroup of a pass gave up waiting for another one of the same launch (bounded
  * spins of the list-parallel sort / blend: never observed; would mean the dispatcher kept a predecessor from running).
  * The frame of that pass is invalid. */
@@ -92,50 +107,52 @@ int hgs_forward_preprocess(void* stream, int P, int D, int M, int W, int H,
 
 /* Forward, part 2: instance scatter (tile binning), per-tile depth sort, front-to-back blend.
  * `R_capacity` = number of instances binning_buf was sized for (== num_rendered in the blocking mode).
- * out_color is [3,H,W].  Fails (status in hgs_read_status) if the scene needs more than R_capacity. */
-int hgs_forward_render(void* stream, int P, int W, int H, int R_capacity, const float* bg,
-                       const float* colors_precomp, void* geom_buf, void* binning_buf, void* image_buf,
-                       float* out_color);
+ * n_extra = 0: bg is [3], out_color [3,H,W].  n_extra = 4, the single-pass mode: RGB + 4 extra unclamped
+ * per-Gaussian channels `extra` [P,4] (16-byte aligned; the reference's mask value and world-space direction) composited with
+ * the same weights in ONE traversal -- what the reference obtains from three separate render() calls per iteration
+ * (train.py:146, loss/losses.py:247 and :312); bg and out_color then have 7 channels.  Workspaces are sized for 3 + n_extra
+ * channels.  flags: how the blend kernels of the pass (and of its backward) get the per-entry records --
+ * HGS_RECORDS_PACKED: the sort kernel writes a 48- / 64-byte record per instance which they stream (rounds 1-5);
+ * HGS_RECORDS_LAZY: the sort kernel orders keys only and they build an entry's record from its Gaussian's template through the
+ * sorted key (nothing is written for the entries behind a tile's last contributor: two thirds of a dense Stage-I frame's);
+ * neither: lazy for passes with at least 128 entries per tile by R_capacity.  Images and gradients are the same bits either way.
+ * Fails (status in hgs_read_status) if the scene needs more than R_capacity. */
+#define HGS_RECORDS_PACKED 16
+#define HGS_RECORDS_LAZY 32
+int hgs_forward_render(void* stream, int P, int W, int H, int R_capacity, int n_extra, int flags,
+                       const float* bg, const float* colors_precomp, const float* extra,
+                       void* geom_buf, void* binning_buf, void* image_buf, float* out_color);
 
-/* Backward.  bg == NULL means a BLACK background (the same gradients as a zero vector; the background terms of the blend
- * backward are compiled out -- what a training step on a black background, train.py:94, should pass).
- * All nine gradient outputs are fully written by the call (zeros for culled Gaussians):
+/* Backward of a pass of hgs_forward_render with the same n_extra.  bg == NULL means a BLACK background (the same gradients as a
+ * zero vector; the background terms of the blend backward are compiled out -- what a training step on a black background,
+ * train.py:94, should pass).  dL_dpix_planes is a HOST array of 3 + n_extra device pointers, one [H,W] gradient plane per
+ * output channel (the planes need not be adjacent: the losses produce them separately).
+ * All gradient outputs are fully written by the call (zeros for culled Gaussians):
  * the caller does not need to zero-fill them (reference zero-allocates, rasterize_points.cu:151-159).
- * dL_dconic is [P,2,2] (element [1,0] is written as 0), dL_dmeans2D is [P,3] (z = 0).
- * `scratch` >= hgs_backward_scratch_bytes(P, R) bytes.  viewmatrix, projmatrix and campos are REQUIRED whatever the colour
- * source (the kernel reads them at entry; NULL is refused). */
-int hgs_backward(void* stream, int P, int D, int M, int R, int W, int H, const float* bg,
+ * dL_dextra is [P,4] (NULL when n_extra is 0); dL_dconic is [P,2,2] (element [1,0] is written as 0); dL_dmeans2D is [P,3]
+ * (z = 0), the screen-space gradient of the RGB channels alone (the only one the reference's densification statistics see);
+ * dL_dmeans3D uses all channels.  `scratch` >= hgs_backward_scratch_bytes(P, R, 3 + n_extra) bytes.  viewmatrix, projmatrix
+ * and campos are REQUIRED whatever the colour source (the kernel reads them at entry; NULL is refused).
+ * flags, with n_extra = 4 (ignored otherwise): the per-Gaussian sums of the instance rows are taken inside the per-Gaussian
+ * launch -- whose wavefronts wait for their longest Gaussian -- (HGS_ROWS_INLINE) or by a launch of their own that is balanced
+ * by ROWS (HGS_ROWS_REDUCE; csrc/hgs_preprocess.hip row_reduce_kernel: runs of 512 rows per wavefront, whatever Gaussians they
+ * belong to): what a pass with many instances per Gaussian wants (a Stage-I cloud at 1080p, the merged strand model: 4 - 12 x
+ * faster); neither: the launch where R >= 8 P.  R is the caller's argument -- in capacity mode a CAPACITY, not a count --, so
+ * a caller that wants the choice to follow the model rather than its capacity sets a bit itself (the Python layer does: from
+ * the instance counts of the warm-up passes of a capture, diff_gaussian_rasterization._C.set_row_reduce).  The same terms
+ * either way, associated differently (rounding); every form is a fixed sequence of additions for a given pass. */
+#define HGS_ROWS_INLINE 64
+#define HGS_ROWS_REDUCE 128
+int hgs_backward(void* stream, int P, int D, int M, int R, int W, int H, int n_extra, int flags, const float* bg,
                  const float* means3D, const float* shs, const float* colors_precomp,
                  const float* scales, float scale_modifier, const float* rotations,
                  const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
                  const float* campos, float tan_fovx, float tan_fovy, const int* radii,
                  const void* geom_buf, const void* binning_buf, const void* image_buf,
-                 const float* dL_dpix, void* scratch,
+                 const float* const* dL_dpix_planes, void* scratch, float* dL_dextra,
                  float* dL_dmeans2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolors,
                  float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
                  float* dL_drotations);
-
-/* Single-pass mode: RGB + 4 extra unclamped per-Gaussian channels (the reference's mask value and
- * world-space direction) composited with the same weights in ONE traversal -- what the reference obtains from three
- * separate render() calls per iteration (train.py:146, loss/losses.py:247 and :312).  hgs_forward_preprocess is
- * shared; bg7 / out_color7 have 7 channels; dL_dpix_planes7 is a HOST array of 7 device pointers, one [H,W] gradient
- * plane per output channel (the planes need not be adjacent: the losses produce them separately); extra4 is [P,4] (16-byte aligned); workspace sizes from the
- * *_multi size functions.  dL_dmeans2D_rgb is the screen-space gradient of the RGB channels alone (the only one
- * the reference's densification statistics see); dL_dmeans3D uses the total. */
-size_t hgs_binning_bytes_multi(int R);
-size_t hgs_backward_scratch_bytes_multi(int P, int R);
-int hgs_forward_render_multi(void* stream, int P, int W, int H, int R_capacity, const float* bg7,
-                             const float* colors_precomp, const float* extra4, void* geom_buf, void* binning_buf,
-                             void* image_buf, float* out_color7);
-int hgs_backward_multi(void* stream, int P, int D, int M, int R, int W, int H, const float* bg7,
-                       const float* means3D, const float* shs, const float* colors_precomp,
-                       const float* scales, float scale_modifier, const float* rotations,
-                       const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                       const float* campos, float tan_fovx, float tan_fovy, const int* radii,
-                       const void* geom_buf, const void* binning_buf, const void* image_buf,
-                       const float* const* dL_dpix_planes7, void* scratch, float* dL_dextra4, float* dL_dmeans2D_rgb,
-                       float* dL_dconic, float* dL_dopacity, float* dL_dcolors, float* dL_dmeans3D,
-                       float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations);
 
 /* present[i] = (view-space z > 0.2)   (cuda_rasterizer/rasterizer_impl.cu:54-66) */
 int hgs_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix,
@@ -348,7 +365,7 @@ int hgs_hair_params_forward(void* stream, int P, const float* endpoints, const l
  *       written by that very launch; the three pointers are used only without a prologue);
  *     - the prologue's zero range must start BEHIND the per-tile instance counters (hgs_image_layout: from
  *       HGS_IMG_TILE_CURSOR on): those must already be zero when the launch starts, which every pass of
- *       hgs_forward_render* in capacity mode leaves behind (its scan clears what it has read); after a pass in blocking mode,
+ *       hgs_forward_render in capacity mode leaves behind (its scan clears what it has read); after a pass in blocking mode,
  *       or on a buffer of unknown content, run hgs_iteration_prologue with the full range of hgs_image_zero_range first. */
 #define HGS_FUSED_PREPROCESS_MAX_TILES 8192
 int hgs_hair_forward_preprocess(void* stream, int P, int D, int M, int W, int H, const float* endpoints,
@@ -374,7 +391,7 @@ int hgs_hair_params_backward(void* stream, int P, int E, const float* endpoints,
                              const HgsStrandFusion* fusion);
 
 /* ---- hgs_backward_multi_params: the BACKWARD mirror of hgs_hair_forward_preprocess / hgs_cloud_forward_preprocess (round 5).
- *   hgs_backward_multi whose last per-Gaussian launch also applies the backward of the derivation parameters -> Gaussian, in the
+ *   hgs_backward (n_extra 4) whose last per-Gaussian launch also applies the backward of the derivation parameters -> Gaussian, in the
  *   lane that has just finished the Gaussian's gradients (they never travel through memory):
  *     HGS_PARAMS_HAIR   what hgs_hair_params_backward's per-segment lanes compute -- d_width, d_opacity_raw, d_mask_raw, the
  *                       densification statistics -- and, in seg_contrib [P][2][4 floats], the gradient of the segment's first and
@@ -383,8 +400,9 @@ int hgs_hair_params_backward(void* stream, int P, int E, const float* endpoints,
  *                       ep_pairs are required: gather mode only) and runs the loss head's deferred tail if one is given.
  *     HGS_PARAMS_CLOUD  everything hgs_cloud_params_backward computes (d_means3D = the rasterizer's dL_dmeans3D); a deferred tail
  *                       (head_tail.out != NULL) rides in a spare workgroup of the launch.  No second launch.
- *   Results are those of hgs_backward_multi + hgs_hair_params_backward (gather mode) / hgs_cloud_params_backward bit for bit.
- *   SH colours, scale_modifier 1 (as the forward entry points).  dL_dsh [P,M,3] is written as hgs_backward_multi writes it.
+ *   Results are those of hgs_backward (n_extra 4) + hgs_hair_params_backward (gather mode) / hgs_cloud_params_backward bit for bit.
+ *   SH colours, scale_modifier 1 (as the forward entry points).  dL_dsh [P,M,3] is written as hgs_backward writes it.
+ *   flags: HGS_ROWS_* as in hgs_backward.
  *   `extra4` / `opacity`-like inputs are the FORWARD's outputs of the same pass.  Optional (NULL = skipped): dL_dmeans2D_rgb
  *   [P,3], the statistics group (max_radii2D / grad_accum / denom, all three or none). ---- */
 enum { HGS_PARAMS_HAIR = 1, HGS_PARAMS_CLOUD = 2 };
@@ -402,10 +420,10 @@ typedef struct HgsParamBackward {
   HgsAdamInline adam;                                                      /* slots with p != NULL: updated by the lane (see HgsAdamSlot) */
 } HgsParamBackward;
 size_t hgs_param_backward_bytes(void);   /* sizeof(HgsParamBackward) */
-int hgs_backward_multi_params(void* stream, int P, int D, int M, int R, int W, int H, const float* bg7, const float* means3D,
-                              const float* shs, const float* scales, const float* rotations, const float* viewmatrix,
-                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
-                              const void* geom_buf, const void* binning_buf, const void* image_buf,
+int hgs_backward_multi_params(void* stream, int P, int D, int M, int R, int W, int H, int flags, const float* bg7,
+                              const float* means3D, const float* shs, const float* scales, const float* rotations,
+                              const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                              float tan_fovy, const int* radii, const void* geom_buf, const void* binning_buf, const void* image_buf,
                               const float* const* dL_dpix_planes7, void* scratch, float* dL_dsh, const HgsParamBackward* params);
 /* d_endpoints [E,3] fully written.  fusion: ep_segments (required), ep_pairs + the smoothness group (smooth_pairs, n_smooth,
  * cos_threshold, eps, head_out, grad_out) and head_tail as for hgs_hair_params_backward; its other groups are ignored. */
@@ -645,40 +663,15 @@ int hgs_raster_resolve(void* stream, int V, int W, int H, int n_models, const Hg
                        const unsigned char* background_host, const int* tile_counts, const long long* tile_offsets,
                        const unsigned* list, unsigned char* rgb, unsigned char* gray);
 
-/* Tile culling (default on).  The reference gives every Gaussian the tiles of its 3-sigma square (forward.cu:229-235,
- * auxiliary.h:46-56) although a pixel only blends it where opacity * exp(power) >= 1/255 (forward.cu:358): with culling on,
- * hgs_forward_preprocess keeps only the tiles that the bounding box of that ellipse reaches, so num_rendered, the tile
- * lists and n_contrib count fewer entries than the reference's -- the dropped ones are skipped by every pixel there too.
- * out_color, radii and all gradients are bit-identical either way.  Off reproduces the reference's lists exactly (the
- * parity tests of the binning stages use it).  Process-wide, takes effect at the next hgs_forward_preprocess; a forward
- * and its backward may run under different settings (the buffers carry the rectangles).  Returns the previous setting. */
-int hgs_set_tile_cull(int on);
-
-/* Development aid (tools/wg_trace.py): when a buffer of 8 uint64 per workgroup of the blend grid (2 T + 1024 is always
- * enough) is registered, blend_fwd / blend_bwd record per workgroup: start, phase marks 1..5, its work item, end (times
- * from s_memrealtime, 100 MHz); NULL (the default) switches it off. */
 /* Tuning knob of the segment-parallel blend (csrc/hgs_blend.hip): tile lists longer than 1.5 segment lengths are walked
  * by one workgroup per segment (the forward walks a list of exactly two segments with one workgroup); the segment length of a pass with R instances is R / target_segments rounded up to a
  * multiple of 64 and clamped to [min_len, max_len] (multiples of 64, min_len >= 128; default 128, 1024, 2048).  Process-wide, takes
  * effect at the next forward pass (a captured graph keeps the policy it was captured with).  Results do not depend
  * on it beyond the association of the per-pixel transmittance product. */
 int hgs_set_segment_policy(int min_len, int max_len, int target_segments);
-/* The 7-channel backward (hgs_backward_multi / hgs_backward_multi_params) takes the per-Gaussian sums of the instance rows either
- * inside its per-Gaussian launch -- whose wavefronts wait for their longest Gaussian -- or with a launch of their own that is
- * balanced by ROWS (csrc/hgs_preprocess.hip row_reduce_kernel: runs of 512 rows per wavefront, whatever Gaussians they belong
- * to): what a pass with many instances per Gaussian wants (a Stage-I cloud at 1080p, the merged strand model: 4 - 12 x faster).
- * mode 1: always the launch; 0: never; -1 (default): where R >= 8 P.  R is the caller's argument -- in capacity mode a CAPACITY,
- * not a count --, so a caller that wants the choice to follow the model rather than its capacity sets 0 / 1 itself (the Python
- * layer does: from the instance counts of the warm-up passes of a capture, diff_gaussian_rasterization._C.set_row_reduce).
- * Process-wide, read by the next backward (a captured graph keeps what it was captured with).  The same terms either way,
- * associated differently (rounding); every form is a fixed sequence of additions for a given pass.  Returns the previous mode. */
-int hgs_set_row_reduce(int mode);
-/* How the blend kernels of the following forward passes (and their backwards) get the per-entry records: 0 = the sort kernel writes a
- * 48- / 64-byte record per instance which they stream (rounds 1-5), 1 = the sort kernel orders keys only and they build an entry's
- * record from its Gaussian's template through the sorted key (nothing is written for the entries behind a tile's last contributor:
- * two thirds of a dense Stage-I frame's), -1 (default) = 1 for passes with at least 128 entries per tile by capacity / exact count.
- * Images and gradients are the same bits either way.  Process-wide; returns the previous setting. */
-int hgs_set_lazy_records(int mode);
+/* Development aid (tools/wg_trace.py): when a buffer of 8 uint64 per workgroup of the blend grid (2 T + 1024 is always
+ * enough) is registered, blend_fwd / blend_bwd record per workgroup: start, phase marks 1..5, its work item, end (times
+ * from s_memrealtime, 100 MHz); NULL (the default) switches it off. */
 int hgs_debug_set_wg_trace(void* device_buf_fwd, void* device_buf_bwd);
 
 /* ---- introspection used by the parity tests (byte offsets of the sub-arrays of each buffer) ---- */

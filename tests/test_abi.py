@@ -46,10 +46,13 @@ def test_workspace_sizes_and_layouts_are_consistent():
         # (between them: the T + 1 row-run marks of HGS_COUNT_ROW_RUNS passes, an even number of words)
         assert lay["tile_cursor"] - lay["tile_count"] == 4 * (slots + ((T + 2) & ~1)) and lay["status"] + 16 <= n
     for R in (0, 1, 1000, 441042):
-        n = L.hgs_binning_bytes(R)
+        n = L.hgs_binning_bytes(R, 3)
         lay = rt.layout("binning", R)
         assert lay["packed"] - lay["point_list"] >= 4 * R and max(lay.values()) + 8 * R <= n
-    assert L.hgs_backward_scratch_bytes(10, 1000) >= 1000 * 48
+        assert L.hgs_binning_bytes(R, 7) >= lay["packed"] + 64 * R   # (7-channel records: 64 bytes)
+    assert L.hgs_backward_scratch_bytes(10, 1000, 3) >= 1000 * 48
+    assert L.hgs_backward_scratch_bytes(10, 1000, 7) >= 1000 * 64 + 10 * 64   # (16-float rows, row_reduce_kernel's row sums)
+    assert L.hgs_binning_bytes(1000, 5) == 0 and L.hgs_backward_scratch_bytes(10, 1000, 4) == 0
 
 
 def test_struct_mirrors_match_the_library():

@@ -62,7 +62,7 @@ ALL = list(VARIANTS) + ["strands", "strands_precomp"]
 
 
 def _forward(s, cull):
-    """Forward pass with tile culling (include/hgs.h hgs_set_tile_cull) on or off; the module default is restored."""
+    """Forward pass with tile culling (include/hgs.h HGS_TILE_CULL) on or off; the module default is restored."""
     from diff_gaussian_rasterization import _C
     from tests import gpu_util as G
     was = _C.set_tile_cull(cull)
@@ -444,29 +444,33 @@ def test_capacity_overflow_gives_zero_gradients_not_garbage(monkeypatch):
     monkeypatch.setenv("HGS_POISON_SCRATCH", "1")
     # (both forms of the blend kernels' records: a lazy pass builds a record THROUGH its sorted key -- the keys of a void pass may
     # never have been written, so its lists must read as empty; round 6's first build followed a stray id out of the buffer)
-    for name, lazy in (("strands", -1), ("dense_long_lists", -1), ("strands", 1), ("dense_long_lists", 1), ("dense_long_lists", 0)):
-        G.rt.lib().hgs_set_lazy_records(lazy)
-        s = _scene(name)
-        full = G.run_forward(s)
-        dpix = np.random.default_rng(4).normal(size=(3, s["H"], s["W"])).astype(np.float32)
-        try:
-            _C.set_async(True)
-            _C._state["cap"] = max(64, full["R"] // 3)
-            fw = G.run_forward(s)
-            assert fw["R"] == _C._state["cap"] and G.intermediates(s, fw)["status"][1] == 1
-            g = G.run_backward(s, fw, dpix)
-            for k, v in g.items():
-                assert np.isfinite(v).all() and (v == 0).all(), k
-            with pytest.raises(_C.HgsCapacityOverflow):
-                _C.check_async()
-            assert _C._state["cap"] > full["R"]
-        finally:
-            _C.set_async(False)
-            _C._state["cap"] = 0
-        # and the same scene right after, with enough capacity, is unaffected
-        g2 = G.run_backward(s, full, dpix)
-        assert any((v != 0).any() for v in g2.values())
-    G.rt.lib().hgs_set_lazy_records(-1)
+    was = _C.set_lazy_records(None)
+    try:
+        for name, lazy in (("strands", None), ("dense_long_lists", None), ("strands", True), ("dense_long_lists", True),
+                           ("dense_long_lists", False)):
+            _C.set_lazy_records(lazy)
+            s = _scene(name)
+            full = G.run_forward(s)
+            dpix = np.random.default_rng(4).normal(size=(3, s["H"], s["W"])).astype(np.float32)
+            try:
+                _C.set_async(True)
+                _C._state["cap"] = max(64, full["R"] // 3)
+                fw = G.run_forward(s)
+                assert fw["R"] == _C._state["cap"] and G.intermediates(s, fw)["status"][1] == 1
+                g = G.run_backward(s, fw, dpix)
+                for k, v in g.items():
+                    assert np.isfinite(v).all() and (v == 0).all(), k
+                with pytest.raises(_C.HgsCapacityOverflow):
+                    _C.check_async()
+                assert _C._state["cap"] > full["R"]
+            finally:
+                _C.set_async(False)
+                _C._state["cap"] = 0
+            # and the same scene right after, with enough capacity, is unaffected
+            g2 = G.run_backward(s, full, dpix)
+            assert any((v != 0).any() for v in g2.values())
+    finally:
+        _C.set_lazy_records(was)
 
 
 def test_empty_inputs():
@@ -636,7 +640,7 @@ def _scene_of(model, cam):
 
 
 def _forward7(s, extra, bg7, cull):
-    """hgs_forward_render_multi through the drop-in module; bg7: a [7] array."""
+    """hgs_forward_render (n_extra 4) through the drop-in module; bg7: a [7] array."""
     import torch
     from diff_gaussian_rasterization import _C
     from tests import gpu_util as G
@@ -774,7 +778,7 @@ def _grad_check7(g, gref, fwd_ref, report_name=None):
 
 @pytest.mark.parametrize("workload", ["north_star", "c2", "c3", "c4", "c5"])
 def test_seven_channel_pass_against_oracle(workload):
-    """hgs_forward_render_multi + hgs_backward_multi (the 7-channel instantiations bench.py times) against three oracle passes
+    """hgs_forward_render + hgs_backward with n_extra 4 (the 7-channel instantiations bench.py times) against three oracle passes
     at the BASELINE sizes: seven image planes, n_contrib / final_T, every gradient as the sum of the three oracle backwards at
     _grad_check's bar, the RGB-only dL_dmeans2D (what densification reads) as the RGB pass's alone.  Twice: bg = NULL (the
     black-background specialisation blend_bwd_kernel<7, true>: the training step's) and a non-zero 7-channel background."""
@@ -809,7 +813,7 @@ def test_seven_channel_pass_against_oracle(workload):
         g = _backward7(s, extra, fw, None if tag == "black" else bg7, dplanes)
         report = _grad_check7(g, gref, ref0)
         if tag == "black":
-            # the same pass with the per-Gaussian row sums taken by row_reduce_kernel (include/hgs.h hgs_set_row_reduce: what
+            # the same pass with the per-Gaussian row sums taken by row_reduce_kernel (include/hgs.h HGS_ROWS_REDUCE: what
             # a pass with many instances per Gaussian runs by default) and with the sums inside the per-Gaussian launch
             from diff_gaussian_rasterization import _C
             was = _C.set_row_reduce(True)
@@ -1049,19 +1053,19 @@ def test_row_run_counting_changes_nothing(name):
 @pytest.mark.parametrize("name", ["strands", "dense_long_lists", "medium_lists", "many_tiles", "one_huge_tile", "sh3_bg", "tiny_image",
                                   "strands_precomp", "c2_full_size", "c3_full_size"])
 def test_lazy_records_change_nothing(name):
-    """hgs_set_lazy_records (include/hgs.h): the blend kernels building an entry's record from its Gaussian's template through the
+    """_C.set_lazy_records (include/hgs.h HGS_RECORDS_*): the blend kernels building an entry's record from its Gaussian's template through the
     sorted key, against streaming the records the sort kernel packs -- image, contributor counts, final transmittance and every
     gradient of the 3-channel pass bit for bit, in the blocking and (the 7-channel pass too: tests/test_gpu_train.py) the capacity
     mode; split lists (dense_long_lists, one_huge_tile, C2 at size), 17 545 tiles, precomputed colours."""
     from diff_gaussian_rasterization import _C
     from tests import gpu_util as G
-    L = G.rt.lib()
     s = _workload_scene(name[:2]) if name.endswith("_full_size") else _scene(name)
     dpix = np.random.default_rng(11).normal(size=(3, s["H"], s["W"])).astype(np.float32)
     runs = {}
+    was = _C.set_lazy_records(None)
     try:
         for lazy in (0, 1):
-            L.hgs_set_lazy_records(lazy)
+            _C.set_lazy_records(lazy)
             fw = G.run_forward(s)
             got = G.intermediates(s, fw)
             assert got["status"][14] == lazy and got["status"][1] == 0
@@ -1078,7 +1082,7 @@ def test_lazy_records_change_nothing(name):
         _C.set_async(True)
         G.run_forward(s)
         for lazy in (0, 1):
-            L.hgs_set_lazy_records(lazy)
+            _C.set_lazy_records(lazy)
             fw = G.run_forward(s)
             assert _C.check_async() == [runs[0][0]["num_rendered"]]
             np.testing.assert_array_equal(fw["color"].cpu().numpy().view(np.uint32), runs[0][0]["out_color"].view(np.uint32))
@@ -1087,4 +1091,4 @@ def test_lazy_records_change_nothing(name):
                 np.testing.assert_array_equal(g[k].view(np.uint32), runs[0][1][k].view(np.uint32), err_msg=k)
     finally:
         _C.set_async(False)
-        L.hgs_set_lazy_records(-1)
+        _C.set_lazy_records(was)

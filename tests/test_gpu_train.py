@@ -1011,7 +1011,7 @@ def test_unread_image_gradient_blocks_change_no_parameter_gradient(workload):
 
 
 def test_black_background_backward_specialisation_is_exact():
-    """hgs_backward_multi(bg = NULL) -- the blend backward with the background terms compiled out, what the fused iteration
+    """hgs_backward(n_extra 4, bg = NULL) -- the blend backward with the background terms compiled out, what the fused iteration
     passes for a black background -- gives the gradients of bg = (0, ..., 0), bit for bit."""
     from arguments import OptimizationParams
     from hgs_runtime.strand_step import FusedStrandStep
@@ -1302,7 +1302,7 @@ def test_one_launch_cloud_parameters_and_preprocess_equals_two_launches():
 def test_fused_parameter_backward_equals_two_launches():
     """hgs_backward_multi_params + hgs_hair_endpoint_gather (round 5: the segment geometry's backward applied in the rasterizer
     backward's per-Gaussian lanes, endpoint contributions instead of 124 bytes of per-Gaussian gradients) against
-    hgs_backward_multi + hgs_hair_params_backward: every parameter gradient, the densification statistics, the RGB-only
+    hgs_backward + hgs_hair_params_backward: every parameter gradient, the densification statistics, the RGB-only
     screen-space gradient and the loss terms BIT FOR BIT (the shared parameter arithmetic is evaluated without contraction in
     both translation units, hgs_strand_bwd.h) -- with the deferred head tail riding in the gather launch and without, with and
     without the smoothness term."""
@@ -1344,7 +1344,7 @@ def test_fused_parameter_backward_equals_two_launches():
 
 
 def test_fused_cloud_parameter_backward_equals_two_launches():
-    """hgs_backward_multi_params(HGS_PARAMS_CLOUD) against hgs_backward_multi + hgs_cloud_params_backward (Stage-I cloud): the
+    """hgs_backward_multi_params(HGS_PARAMS_CLOUD) against hgs_backward + hgs_cloud_params_backward (Stage-I cloud): the
     launch of the parameters' backward is gone, its results -- gradients of all seven parameter groups, statistics, loss terms
     (the deferred tail rides in the rasterizer backward's spare workgroup) -- bit for bit."""
     from arguments import OptimizationParams
@@ -1881,10 +1881,9 @@ def test_device_strand_walk_equals_the_host_walk(seed):
 
 @pytest.mark.parametrize("kind", ["cloud", "strands"])
 def test_lazy_records_in_the_fused_iterations(kind):
-    """hgs_set_lazy_records in the single-pass 7-channel iteration (capacity mode, the one-launch parameter + preprocess kernels, the
+    """_C.set_lazy_records in the single-pass 7-channel iteration (capacity mode, the one-launch parameter + preprocess kernels, the
     row sums by row_reduce_kernel for the cloud): records built by the blend kernels against records packed by the sort kernel --
     loss terms, image planes, radii and every parameter gradient bit for bit over six iterations."""
-    import hgs_runtime as rt
     from arguments import OptimizationParams
     from diff_gaussian_rasterization import _C as raster
     from hgs_runtime.strand_step import FusedCloudStep, FusedStrandStep, ViewTable
@@ -1902,11 +1901,12 @@ def test_lazy_records_in_the_fused_iterations(kind):
     params = ([model._xyz, model._scaling, model._rotation, model._opacity, model._mask, model._features_dc] if kind == "cloud"
               else [model._endpoints, model._width, model._opacity, model._mask, model._features_dc])
     out = {}
+    was = raster.set_lazy_records(None)
     try:
         raster._state["cap"] = 0
         raster.set_async(True, slack=2.0)
         for lazy in (0, 1):
-            rt.lib().hgs_set_lazy_records(lazy)
+            raster.set_lazy_records(lazy)
             views = ViewTable(cams)
             step = (FusedCloudStep if kind == "cloud" else FusedStrandStep)(model, views, opt, torch.zeros(3, device="cuda"))
             seen = []
@@ -1922,7 +1922,7 @@ def test_lazy_records_in_the_fused_iterations(kind):
             out[lazy] = seen
     finally:
         raster.set_async(False)
-        rt.lib().hgs_set_lazy_records(-1)
+        raster.set_lazy_records(was)
     for a, b in zip(out[0], out[1]):
         for x, y in zip(a, b):
             assert torch.equal(x, y)
