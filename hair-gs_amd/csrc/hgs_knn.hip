@@ -17,20 +17,12 @@
 #include <float.h>
 
 #include "hgs_common.h"
+#include "hgs_keysort.h"   // prep_morton, the bitonic kernels, pad_pow2, keysort_launch
 
 namespace {
 
-#define KNN_LDS_KEYS 4096
-
 struct KnnScratch { float* minmax; uint64_t* keys; float4* sorted; uint32_t* cells; };   // cells: 8 words per cell
 
-__device__ __forceinline__ uint32_t prep_morton(uint32_t x) {
-  x = (x | (x << 16)) & 0x030000FF;
-  x = (x | (x << 8)) & 0x0300F00F;
-  x = (x | (x << 4)) & 0x030C30C3;
-  x = (x | (x << 2)) & 0x09249249;
-  return x;
-}
 __device__ __forceinline__ uint32_t f2u_sat(float v) {
   if (!(v > 0.f)) return 0u;
   if (v >= 4294967040.f) return 0xFFFFFFFFu;
@@ -85,40 +77,6 @@ __global__ __launch_bounds__(256) void morton_kernel(int P, int Npad, const floa
   const uint32_t cy = prep_morton(f2u_sat(((y - mny) / (mxy - mny)) * 1023));
   const uint32_t cz = prep_morton(f2u_sat(((z - mnz) / (mxz - mnz)) * 1023));
   keys[i] = ((uint64_t)(cx | (cy << 1) | (cz << 2)) << 32) | (uint32_t)i;
-}
-
-// bitonic steps j = jstart .. 1 of stage k inside LDS chunks of KNN_LDS_KEYS keys (jstart < KNN_LDS_KEYS);
-// with full=true runs every stage k = 2..KNN_LDS_KEYS (initial chunk sort)
-__global__ __launch_bounds__(1024) void bitonic_lds_kernel(uint64_t* __restrict__ keys, int k_stage, int jstart, bool full) {
-  __shared__ uint64_t sk[KNN_LDS_KEYS];
-  const size_t base = (size_t)blockIdx.x * KNN_LDS_KEYS;
-  for (int i = threadIdx.x; i < KNN_LDS_KEYS; i += 1024) sk[i] = keys[base + i];
-  __syncthreads();
-  const int k0 = full ? 2 : k_stage, k1 = full ? KNN_LDS_KEYS : k_stage;
-  for (int k = k0; k <= k1; k <<= 1) {
-    for (int j = full ? (k >> 1) : jstart; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < KNN_LDS_KEYS / 2; t += 1024) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const int l = i | j;
-        const bool asc = (((base + i) & (size_t)k) == 0);
-        const uint64_t x = sk[i], y = sk[l];
-        if ((x > y) == asc) { sk[i] = y; sk[l] = x; }
-      }
-      __syncthreads();
-    }
-    if (!full) break;
-  }
-  for (int i = threadIdx.x; i < KNN_LDS_KEYS; i += 1024) keys[base + i] = sk[i];
-}
-
-__global__ __launch_bounds__(256) void bitonic_global_kernel(uint64_t* __restrict__ keys, size_t half, int k, int j) {
-  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= half) return;
-  const size_t i = ((t & ~((size_t)j - 1)) << 1) | (t & ((size_t)j - 1));
-  const size_t l = i | (size_t)j;
-  const bool asc = (i & (size_t)k) == 0;
-  const uint64_t x = keys[i], y = keys[l];
-  if ((x > y) == asc) { keys[i] = y; keys[l] = x; }
 }
 
 __global__ __launch_bounds__(256) void gather_kernel(int P, const float* __restrict__ pts, const uint64_t* __restrict__ keys,
@@ -256,12 +214,6 @@ size_t knn_carve(char* base, size_t P, size_t Npad, KnnScratch& s) {
   hgs_carve(cur, s.cells, 8 * ((size_t)1 << (3 * knn_level(P))));
   return hgs_align_up((size_t)(cur - base)) + HGS_ALIGN;
 }
-size_t pad_pow2(size_t P) {
-  size_t n = KNN_LDS_KEYS;
-  while (n < P) n <<= 1;
-  return n;
-}
-
 }  // namespace
 
 size_t hgs_dist2_scratch(int P) {
@@ -280,14 +232,7 @@ int hgs_launch_dist2(hipStream_t st, int P, const float* points, float* out, voi
   HgsProfScope _prof(st, HGS_K_KNN);
   hipLaunchKernelGGL(minmax_kernel, dim3(MM_BLOCKS), dim3(1024), 0, st, P, points, s.minmax);
   hipLaunchKernelGGL(morton_kernel, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, st, P, (int)Npad, points, s.minmax, s.keys);
-  const unsigned nchunks = (unsigned)(Npad / KNN_LDS_KEYS);
-  hipLaunchKernelGGL(bitonic_lds_kernel, dim3(nchunks), dim3(1024), 0, st, s.keys, 0, 0, true);
-  for (size_t k = 2 * KNN_LDS_KEYS; k <= Npad; k <<= 1) {
-    size_t j = k >> 1;
-    for (; j >= KNN_LDS_KEYS; j >>= 1)
-      hipLaunchKernelGGL(bitonic_global_kernel, dim3((unsigned)((Npad / 2 + 255) / 256)), dim3(256), 0, st, s.keys, Npad / 2, (int)k, (int)j);
-    hipLaunchKernelGGL(bitonic_lds_kernel, dim3(nchunks), dim3(1024), 0, st, s.keys, (int)k, (int)j, false);
-  }
+  keysort_launch(st, s.keys, Npad);
   const int L = knn_level((size_t)P);
   const unsigned n_cells = 1u << (3 * L);
   hipLaunchKernelGGL(gather_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, points, s.keys, s.sorted);

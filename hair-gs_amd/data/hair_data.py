@@ -71,7 +71,8 @@ def _append(strands, edges, colors, roots, ids, xyz, color, last):
     return last + n
 
 
-def load_hair_from_usc_dataset(file_path, normal_required=False, hsv_spectre_color=True, pct_strands=100):
+def load_hair_from_usc_dataset(file_path, normal_required=False, hsv_spectre_color=True, pct_strands=100, normals_device=None):
+    """normals_device: None = the host path of utils.normals, "cuda" = its HIP kernels."""
     with open(file_path, "rb") as fh:
         buf = fh.read()
     (num_strands,) = struct.unpack_from("<i", buf, 0)
@@ -92,7 +93,7 @@ def load_hair_from_usc_dataset(file_path, normal_required=False, hsv_spectre_col
     normals = None
     if normal_required:
         from utils.normals import estimate_pointcloud_normals
-        normals = estimate_pointcloud_normals(np.concatenate(strands, axis=0))
+        normals = estimate_pointcloud_normals(np.concatenate(strands, axis=0), device=normals_device)
     return _finish(strands, colors, normals, edges, roots, ids)
 
 

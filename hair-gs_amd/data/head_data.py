@@ -1,7 +1,7 @@
 """Head meshes of the synthetic datasets (the reference's data/head_data.py), with a small OBJ reader in place of pytorch3d's
 load_obj (not installed here).  Heads are grey (0.75, 0.75, 0.75, 1).  Normals: one per face -> every vertex of the face takes it
 (the last face written wins), one per vertex -> as they are, any other count -> estimated from the vertices
-(utils.normals.estimate_pointcloud_normals)."""
+(utils.normals.estimate_pointcloud_normals; normals_device = None: its host path, "cuda": its HIP kernels)."""
 from typing import NamedTuple
 
 import numpy as np
@@ -44,30 +44,30 @@ def load_obj(path):
     return v, f, np.array(normals, dtype=np.float32).reshape(-1, 3)
 
 
-def _vertex_normals(verts, faces, normals):
+def _vertex_normals(verts, faces, normals, normals_device=None):
     if normals.shape[0] == faces.shape[0]:
         out = np.zeros((verts.shape[0], 3))
         out[faces.reshape(-1)] = np.repeat(normals, 3, axis=0)
         return out
     if normals.shape[0] != verts.shape[0]:
         from utils.normals import estimate_pointcloud_normals
-        return estimate_pointcloud_normals(verts)
+        return estimate_pointcloud_normals(verts, device=normals_device)
     return normals
 
 
-def load_head_from_usc_dataset(file_path, normal_required=False):
+def load_head_from_usc_dataset(file_path, normal_required=False, normals_device=None):
     verts, faces, normals = load_obj(file_path)
     return HeadData(verts=verts, colors=np.tile(HEAD_COLOR, (verts.shape[0], 1)),
-                    normals=_vertex_normals(verts, faces, normals) if normal_required else None, faces=faces)
+                    normals=_vertex_normals(verts, faces, normals, normals_device) if normal_required else None, faces=faces)
 
 
-def load_head_from_cy_dataset(file_path):
+def load_head_from_cy_dataset(file_path, normals_device=None):
     from data.hair_data import zup_to_yup
     verts, faces, normals = load_obj(file_path)
     verts = 0.25 * verts.astype(np.float64) / 100
     verts = (zup_to_yup() @ verts.T).T
-    return HeadData(verts=verts, colors=np.tile(HEAD_COLOR, (verts.shape[0], 1)), normals=_vertex_normals(verts, faces, normals),
-                    faces=faces)
+    return HeadData(verts=verts, colors=np.tile(HEAD_COLOR, (verts.shape[0], 1)),
+                    normals=_vertex_normals(verts, faces, normals, normals_device), faces=faces)
 
 
 head_data_load_callbacks = {"usc_hair_salon": load_head_from_usc_dataset, "cem_yuksel": load_head_from_cy_dataset}

@@ -77,6 +77,8 @@ SIGNATURES = {
     "hgs_radius_pairs": (ci, [vp, ci, vp, vp, cf, cf, ci, ci, vp, vp, vp, ci]),
     "hgs_knn3": (ci, [vp, ci, vp, vp, vp]),
     "hgs_nearest_distance_f64": (ci, [vp, ci, ci, vp, vp, vp]),
+    "hgs_pointcloud_normals_scratch_bytes": (sz, [ci, ci]),
+    "hgs_pointcloud_normals": (ci, [vp, ci, ci, vp, vp, vp, vp, sz]),
     "hgs_strand_walk_ends": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp]),
     "hgs_strand_walk_fill": (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp]),
     "hgs_strand_grow_plan": (ci, [vp, ci, vp, vp, vp, ci, vp, ci, ci, ci, cf, vp, vp, vp]),
@@ -192,7 +194,7 @@ HEAD_OUT = ["total", "l1", "dssim", "mask", "orientation", "smooth", "ori_count"
             "g_ori", "g_smooth", "total_fwd"]
 HEAD_NOUT = 16
 FUSED_PREPROCESS_MAX_TILES = 8192   # include/hgs.h HGS_FUSED_PREPROCESS_MAX_TILES
-ABI_VERSION = 9   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
+ABI_VERSION = 10   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
 
 
 def build(verbose=False):

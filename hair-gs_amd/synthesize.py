@@ -3,13 +3,15 @@
 (scripts/parse_usc_hairsalon.py, scripts/download_parse_cy.py), with the rasterizer of scene/mesh_renderer.py in place of OpenGL.
   python synthesize.py --dataset usc_hair_salon|cem_yuksel --hair <strands file> --head <obj> -o <scene>
       [--pct_strands 100] [--line_width 1] [--hsv] [--cam_z (0.5 usc / 0.3 cy)] [--cameras 16] [--height 1000] [--width 1000]
-      [--use_gt_hair_verts | --use_strand_root_verts] [--device cuda|cpu] [--batch 16] [--overwrite]
+      [--use_gt_hair_verts | --use_strand_root_verts] [--device cuda|cpu] [--normals host|device] [--batch 16] [--overwrite]
 Writes <scene>/images/image_<id>.png (the lit head and the hair), masks/image_<id>.png (255 where the render of the black head and
 the hair is not black), orientations/image_<id>_{orientation,confidence}.png (utils.vision, as orient.py writes them),
 hair_eval_data.npz, head_reconstruction_data.npz and sparse/0/{cameras,images,points3D}.bin.  The models are [black unlit head,
 lit head (ka = kd = 0.5), lit hair], lit from (0, 5, 5) in white; the cameras ring the hair at its mid-height.  On the GPU the
 images, masks and orientation maps of a batch stay on the device until the PNGs are written.  An existing output folder is
-refused unless --overwrite is given."""
+refused unless --overwrite is given.  --normals device estimates the hair's (and, where the head file has none, the head's) vertex
+normals with the HIP kernels of utils.normals instead of the host's k-d tree (needs --device cuda; same contract, last-place
+differences: the default stays host so that existing captures keep their bytes)."""
 import os
 import shutil
 import sys
@@ -115,9 +117,13 @@ def main(argv=None):
     init.add_argument("--use_gt_hair_verts", action="store_true", help="initial point cloud: the hair vertices")
     init.add_argument("--use_strand_root_verts", action="store_true", help="initial point cloud: the strand roots")
     parser.add_argument("--device", default="cuda", help="cuda: the HIP kernels; cpu: the CPU path")
+    parser.add_argument("--normals", default="host", choices=["host", "device"],
+                        help="vertex normals: host = scipy k-d tree + LAPACK; device = the HIP kernels (needs --device cuda)")
     parser.add_argument("--batch", type=int, default=16, help="views per render call")
     parser.add_argument("--overwrite", action="store_true", help="replace an existing output folder")
     args = parser.parse_args(argv)
+    if args.normals == "device" and args.device == "cpu":
+        parser.error("--normals device needs a GPU: it cannot be combined with --device cpu")
     from data.colmap import generate_colmap_data, write_cameras_binary, write_images_binary, write_points3D_binary
     from data.hair_data import hair_data_load_callbacks, save_hair_eval_data_npz
     from data.head_data import head_data_load_callbacks
@@ -128,14 +134,15 @@ def main(argv=None):
             raise SystemExit(f"synthesize.py: {out} exists (--overwrite replaces it)")
         shutil.rmtree(out)
     device = None if args.device == "cpu" else args.device
+    normals_device = args.device if args.normals == "device" else None
     cam_z = args.cam_z if args.cam_z is not None else (0.5 if args.dataset == "usc_hair_salon" else 0.3)
     t0 = time.time()
     if args.dataset == "usc_hair_salon":
-        head = head_data_load_callbacks["usc_hair_salon"](args.head, normal_required=True)
+        head = head_data_load_callbacks["usc_hair_salon"](args.head, normal_required=True, normals_device=normals_device)
         hair = hair_data_load_callbacks["usc_hair_salon"](args.hair, normal_required=True, hsv_spectre_color=args.hsv,
-                                                          pct_strands=args.pct_strands)
+                                                          pct_strands=args.pct_strands, normals_device=normals_device)
     else:
-        head = head_data_load_callbacks["cem_yuksel"](args.head)
+        head = head_data_load_callbacks["cem_yuksel"](args.head, normals_device=normals_device)
         hair = hair_data_load_callbacks["cem_yuksel"](args.hair, hsv_spectre_color=args.hsv, pct_strands=args.pct_strands)
     t1 = time.time()
     cams, Es = ring_cameras(hair, args.cameras, args.height, args.width, cam_z)
@@ -159,7 +166,8 @@ def main(argv=None):
     write_images_binary(images, os.path.join(sparse, "images.bin"))
     write_points3D_binary(points3d, os.path.join(sparse, "points3D.bin"))
     print(f"synthesize.py: {len(ids)} views of {hair.edges.shape[0]} segments and {head.faces.shape[0]} triangles -> {out} "
-          f"(load {t1 - t0:.1f} s, render + orientation {t2 - t1:.1f} s, {dropped} dropped primitive(s))")
+          f"(load {t1 - t0:.1f} s, render + orientation {t2 - t1:.1f} s, {dropped} dropped primitive(s), "
+          f"normals: {args.normals})")
     return dropped
 
 

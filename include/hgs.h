@@ -48,9 +48,9 @@ extern "C" {
  * 6, round 6: tile_delta in the image buffer; 7: every image-buffer field behind tile_cursor starts on a 256-byte boundary, and a
  * misaligned HgsHeadParams.tile_used is an error of hgs_loss_head_forward; 8: hgs_strand_grow_plan / hgs_strand_grow_fill;
  * 9: tile culling, the record form and the row sums are flag bits of each call instead of process-wide setters, and one render,
- * backward and size function each serves 3 and 7 channels);
+ * backward and size function each serves 3 and 7 channels; 10: hgs_pointcloud_normals / hgs_pointcloud_normals_scratch_bytes);
  * the Python binding refuses a library whose version or struct sizes differ from its own */
-#define HGS_ABI_VERSION 9
+#define HGS_ABI_VERSION 10
 #define HGS_TILE 16 /* cuda_rasterizer/config.h:16-17 */
 
 int hgs_abi_version(void);
@@ -540,6 +540,16 @@ int hgs_knn3(void* stream, int N, const float* points, int* idx /* [N,3] */, flo
  *   (scene/hair_gaussian_model.py:1466-1470): out[i] = min_m |points[i] - refs[m]| in float64 (points float32 [N,3], refs
  *   float64 [M,3], M >= 1). */
 int hgs_nearest_distance_f64(void* stream, int N, int M, const float* points, const double* refs, double* out);
+/* hgs_pointcloud_normals <-> pytorch3d.ops.estimate_pointcloud_normals as the reference's hair and head loaders call it
+ *   (data/hair_data.py:124-128, data/head_data.py:40-43); the contract is the docstring of utils/normals.py (csrc/hgs_normals.hip).
+ *   points float64 [N,3] (finite: the caller checks); for every point its K nearest points of the same set, itself included, by
+ *   d2 = (dx*dx + dy*dy) + dz*dz in float64, equal d2 in ascending index order; normals[i] = the unit eigenvector of the smallest
+ *   eigenvalue of their covariance, negated when fewer than K / 2 neighbours q have (q - p) . n > 0; neighbors (nullable):
+ *   the K indices in rank order.  1 <= K <= 64, K <= N, N <= 2^27 = 134217728 (32-bit keys and positions); N = 0 returns 0
+ *   without a launch.  scratch: >= hgs_pointcloud_normals_scratch_bytes(N, K) bytes, 256-byte aligned. */
+size_t hgs_pointcloud_normals_scratch_bytes(int N, int K);
+int hgs_pointcloud_normals(void* stream, int N, int K, const double* points /* [N,3] */, double* normals /* [N,3] */,
+                           int* neighbors /* [N,K] in rank order, or NULL */, void* scratch, size_t scratch_bytes);
 /* hgs_strand_walk_ends / hgs_strand_walk_fill <-> the walk over every open polyline of the segment table in compute_strands_info
  *   (scene/hair_gaussian_model.py:1410-1498; its per-strand Python loop :1432-1464).  pairs[n][2]: endpoint ids of the segments
  *   (every id of degree 1 or 2, ids < n_ep).
