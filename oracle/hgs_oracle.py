@@ -120,9 +120,11 @@ def forward(inp, f64=False, render=True):
     return o
 
 
-def backward(inp, fwd, dL_dpix, f64=False):
+def backward(inp, fwd, dL_dpix, f64=False, pixel_mask=False):
     """Full backward given the forward's intermediates.  Output names/shapes follow
-    DGR/rasterize_points.cu:151-159 (dL_dconic is [P,2,2] with element [1,0] unused)."""
+    DGR/rasterize_points.cu:151-159 (dL_dconic is [P,2,2] with element [1,0] unused).
+    pixel_mask=True adds g["fragile_pixels"], an [H, W] bool array of the pixels that hold a near-threshold decision
+    (raster_oracle.c; it depends on the forward state only, not on dL_dpix)."""
     dt, cr, sfx = _real(f64)
     L = lib()
     n = normalize_inputs(inp, f64)
@@ -132,10 +134,12 @@ def backward(inp, fwd, dL_dpix, f64=False):
     acc = np.zeros((P, 9), np.float64)
     fragile = np.zeros(P, np.uint8)   # Gaussians with a near-threshold (pixel, entry) decision (raster_oracle.c)
     touched = np.zeros(P, np.uint8)   # Gaussians blended at a pixel that holds such a decision (its transmittance chain moves)
+    pmask = np.zeros(H * W, np.uint8) if pixel_mask else None
     getattr(L, "hgs_oracle_render_backward" + sfx)(C.c_int(P), C.c_int(W), C.c_int(H), _p(fwd["ranges"]),
                                                    _p(fwd["point_list"]), _p(n["bg"]), _p(fwd["means2D"]),
                                                    _p(fwd["conic_opacity"]), _p(feats), _p(fwd["final_T"]),
-                                                   _p(fwd["n_contrib"]), _p(dpix), _p(acc), _p(fragile), _p(touched))
+                                                   _p(fwd["n_contrib"]), _p(dpix), _p(acc), _p(fragile), _p(touched),
+                                                   _p(pmask))
     g = {
         "dL_dmeans2D": np.zeros((P, 3), dt), "dL_dconic": np.zeros((P, 4), dt), "dL_dopacity": np.zeros((P, 1), dt),
         "dL_dcolors": np.zeros((P, 3), dt), "dL_dmeans3D": np.zeros((P, 3), dt), "dL_dcov3D": np.zeros((P, 6), dt),
@@ -157,7 +161,27 @@ def backward(inp, fwd, dL_dpix, f64=False):
     g["acc"] = acc
     g["fragile"] = fragile.astype(bool)
     g["touched"] = touched.astype(bool) | g["fragile"]
+    if pixel_mask:
+        g["fragile_pixels"] = pmask.astype(bool).reshape(H, W)
     return g
+
+
+def fragile_pixels(inp, fwd, f64=False):
+    """[H, W] bool: the pixels of the forward state `fwd` (ranges, point_list, n_contrib, ...) whose walk evaluates an entry
+    within 1e-4 of alpha * 255 = 1 or within 1e-5 of power = 0 -- where another exp may take the decision the other way.
+    Independent of any dL_dpix: a test calls this first and zeroes its dL_dpix on the mask."""
+    dt, _, sfx = _real(f64)
+    n = normalize_inputs(inp, f64)
+    P, W, H = n["P"], int(n["W"]), int(n["H"])
+    feats = n["colors_precomp"] if n["colors_precomp"] is not None else fwd["rgb"]
+    acc = np.zeros((P, 9), np.float64)
+    pmask = np.zeros(H * W, np.uint8)
+    getattr(lib(), "hgs_oracle_render_backward" + sfx)(C.c_int(P), C.c_int(W), C.c_int(H), _p(fwd["ranges"]),
+                                                       _p(fwd["point_list"]), _p(n["bg"]), _p(fwd["means2D"]),
+                                                       _p(fwd["conic_opacity"]), _p(feats), _p(fwd["final_T"]),
+                                                       _p(fwd["n_contrib"]), _p(np.zeros((3, H, W), dt)), _p(acc), None, None,
+                                                       _p(pmask))
+    return pmask.astype(bool).reshape(H, W)
 
 
 def mark_visible(means3D, viewmatrix):

@@ -429,10 +429,12 @@ void SYM(hgs_oracle_render_backward)(int P, int W, int H, const uint32_t* ranges
                                      const real* final_Ts, const uint32_t* n_contrib, const real* dL_dpixels,
                                      double* acc /* [P][9], zeroed here */,
                                      uint8_t* fragile /* [P] or NULL: see below */,
-                                     uint8_t* touched /* [P] or NULL: see below */) {
+                                     uint8_t* touched /* [P] or NULL: see below */,
+                                     uint8_t* pixel_mask /* [H*W] or NULL: 1 where the pixel holds such a decision */) {
   const int gx = (W + BLOCK_X - 1) / BLOCK_X, gy = (H + BLOCK_Y - 1) / BLOCK_Y;
   memset(acc, 0, (size_t)P * 9 * sizeof(double));
   const real ddelx_dx = (real)(0.5 * W), ddely_dy = (real)(0.5 * H);
+  const int mark = fragile != NULL || pixel_mask != NULL; /* look for near-threshold decisions at all */
 #pragma omp parallel for schedule(dynamic, 1)
   for (int tile = 0; tile < gx * gy; tile++) {
     int tx = tile % gx, ty = tile / gx;
@@ -459,7 +461,7 @@ void SYM(hgs_oracle_render_backward)(int P, int W, int H, const uint32_t* ranges
           const real* co = conic_opacity + 4 * (size_t)id;
           real power = (real)-0.5 * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy;
           if (power > 0) {
-            if (fragile && (double)power < 1e-5) { fragile[id] = 1; pixel_fragile = 1; }
+            if (mark && (double)power < 1e-5) { if (fragile) fragile[id] = 1; pixel_fragile = 1; }
             continue;
           }
           real G = R_EXP(power);
@@ -469,7 +471,7 @@ void SYM(hgs_oracle_render_backward)(int P, int W, int H, const uint32_t* ranges
            * implementation whose exp differs by an ulp may branch the other way there (the CUDA reference against
            * any CPU code has the same property).  Tests bound the number of such Gaussians and hold every other
            * one to the tolerance. */
-          if (fragile && (fabs((double)alpha * 255.0 - 1.0) < 1e-4 || fabs((double)power) < 1e-5)) { fragile[id] = 1; pixel_fragile = 1; }
+          if (mark && (fabs((double)alpha * 255.0 - 1.0) < 1e-4 || fabs((double)power) < 1e-5)) { if (fragile) fragile[id] = 1; pixel_fragile = 1; }
           if (alpha < (real)1.0 / (real)255.0) continue;
           T = T / ((real)1.0 - alpha);
           real dchannel_dcolor = alpha * T;
@@ -513,7 +515,10 @@ void SYM(hgs_oracle_render_backward)(int P, int W, int H, const uint32_t* ranges
         /* Checker aid, second part: a decision that an implementation takes the other way changes this PIXEL's transmittance
          * chain by that entry's alpha (~1/255) and the colour behind every nearer entry -- i.e. the terms of EVERY Gaussian the
          * pixel blends by up to ~0.4 % of what the pixel contributes to them, not only the fragile one's.  Those Gaussians are
-         * enumerated too (`touched`): the pixel's walk is repeated and every blended entry marked. */
+         * enumerated too (`touched`): the pixel's walk is repeated and every blended entry marked.  The pixels themselves are
+         * exported as `pixel_mask`: every term a pixel contributes is linear in its dL_dpixel, so a caller that zeroes dL_dpixel
+         * there gets gradients that no such decision can move. */
+        if (pixel_mask) pixel_mask[pix_id] = (uint8_t)pixel_fragile;
         if (touched && pixel_fragile) {
           uint32_t c2 = r1 - r0;
           for (uint32_t k = 0; k < r1 - r0; k++) {

@@ -147,6 +147,53 @@ def strand_scene(n_strands=20, n_seg=50, W=160, H=96, seed=0, bg=(0.0, 0.0, 0.0)
     return scene
 
 
+# The adversarial scenes of the rasterizer parity tests (tests/test_gpu_raster.py on the GPU, tests/test_oracle_checks.py on
+# the CPU): each exists because kernels go wrong there.
+VARIANTS = {
+    "sh0": dict(P=1500, W=160, H=96, seed=1, sh_degree=0),
+    "sh3_bg": dict(P=1200, W=130, H=75, seed=2, sh_degree=3, bg=(0.1, 0.2, 0.3)),          # W,H not multiples of 16
+    "sh1_M16": dict(P=600, W=96, H=64, seed=3, sh_degree=1, M=16),                           # active degree < stored
+    "precomp_neg": dict(P=900, W=96, H=64, seed=4, use_colors_precomp=True, neg_colors=True, bg=(1.0, 1.0, 1.0)),
+    "cov_precomp": dict(P=900, W=96, H=64, seed=5, use_cov3D_precomp=True, sh_degree=2),
+    "dense_long_lists": dict(P=6000, W=64, H=48, seed=6, sh_degree=0, scale_lo=0.03, scale_hi=0.12,
+                             opacity_lo=0.01, opacity_hi=0.08),                              # ~3000 entries per tile: 6 sort chunks, 24 blend segments
+    # lists of ~1000 entries: split into blend segments, one sort chunk
+    "medium_lists": dict(P=2500, W=64, H=48, seed=15, sh_degree=1, scale_lo=0.03, scale_hi=0.1, opacity_lo=0.02,
+                         opacity_hi=0.3, bg=(0.2, 0.1, 0.4)),
+    # ONE tile with > 63 x 512 entries: more sort chunks / blend segments than cooperate (serial sort fallback, longer segments),
+    # and the stop rule reached deep inside the list
+    "one_huge_tile": dict(P=140000, W=16, H=16, seed=14, spread=0.02, scale_lo=0.02, scale_hi=0.05, opacity_lo=0.003,
+                          opacity_hi=0.012, behind_frac=0.0),
+    "opaque_early_stop": dict(P=3000, W=96, H=64, seed=7, sh_degree=0, scale_lo=0.05, scale_hi=0.2,
+                              opacity_lo=0.9, opacity_hi=0.99),                              # saturation / early exit
+    "depth_ties": dict(P=3000, W=200, H=120, seed=11, depth_levels=6, scale_lo=0.01, scale_hi=0.06),
+    # camera far off the +z axis: view rotation of ~120 degrees about y and ~35 degrees of pitch
+    "rotated_cam": dict(P=1500, W=160, H=96, seed=12, sh_degree=2, eye=(1.0, -0.7, 0.55), behind_frac=0.0, fovx_deg=90.0),
+    # the viewer's scaling_modifier (render(..., scaling_modifier), CR/forward.cu:118-150 computeCov3D; its backward :600-650)
+    "scale_modifier": dict(P=1200, W=128, H=80, seed=21, sh_degree=1, scale_modifier=0.6),
+    "all_culled": dict(P=300, W=64, H=64, seed=8, behind_frac=1.0),
+    "tiny_image": dict(P=200, W=7, H=5, seed=9),
+    # 145 x 121 = 17545 tiles (> 16384: the scan kernel's chunked path) and footprints of hundreds of tiles (the direct
+    # global-atomic path of the counting / scatter kernels)
+    "many_tiles": dict(P=400, W=2320, H=1936, seed=13, sh_degree=1),
+    # 160 x 90 = 14400 tiles: the largest share (2048 tiles per builder) the work-list builders still keep in LDS, i.e. the
+    # form that shares the counting; many_tiles is the single-builder form
+    "qhd_tiles": dict(P=400, W=2560, H=1440, seed=14, sh_degree=0),
+}
+
+
+def _scene(name):
+    if name == "strands":
+        return strand_scene(n_strands=60, n_seg=60, W=256, H=144, seed=3)
+    if name == "strands_precomp":
+        return strand_scene(n_strands=40, n_seg=50, W=200, H=120, seed=4, use_colors_precomp=True,
+                            bg=(0.3, 0.3, 0.3))
+    return random_scene(**VARIANTS[name])
+
+
+ALL = list(VARIANTS) + ["strands", "strands_precomp"]
+
+
 def c1_cloud(device="cpu", n_strands=50, n_seg=20, seed=3):
     """BASELINE.json config C1: a 1k-Gaussian Stage-I cloud for merge.py -- every Gaussian is one segment of one of
     n_strands polylines (line-like: main axis = half length x dist_to_scale_factor, 0.1 mm across), stored in shuffled

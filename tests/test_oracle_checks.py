@@ -1,5 +1,6 @@
 """Independent checks of the (reference-unpinned) oracle arithmetic:
-fp64 central finite differences of the backward, and a brute-force 3-NN for distCUDA2."""
+fp64 central finite differences of the backward, a brute-force 3-NN for distCUDA2, and the per-pixel mask of near-threshold
+decisions that the strict GPU gradient checks zero dL_dpix on (tests/test_gpu_raster.py _grad_check_strict)."""
 import numpy as np
 import pytest
 
@@ -27,6 +28,17 @@ def test_backward_matches_finite_differences(variant):
             s[k] = np.asarray(s[k], np.float64)
     rng = np.random.default_rng(7)
     dpix = rng.normal(size=(3, s["H"], s["W"]))
+    _fd_check(s, dpix, rng)
+    # the same with dpix zeroed on the pixels that hold a near-threshold decision (what the strict GPU gradient check feeds
+    # both sides): the masked loss is a loss the oracle differentiates correctly too
+    mask = O.fragile_pixels(s, O.forward(s, f64=True), f64=True)
+    assert mask.shape == (s["H"], s["W"]) and mask.dtype == bool
+    print(variant, "masked pixels", int(mask.sum()), "of", mask.size)
+    _fd_check(s, dpix * ~mask, np.random.default_rng(8))
+
+
+def _fd_check(s, dpix, rng):
+    """Analytic f64 backward of sum(out_color * dpix) against central differences on sampled elements of every input."""
     L0, f = _loss(s, dpix)
     g = O.backward(s, f, dpix, f64=True)
     pairs = [("means3D", "dL_dmeans3D"), ("opacities", "dL_dopacity"), ("shs", "dL_dsh"),
@@ -131,3 +143,103 @@ def test_binning_is_sorted_and_stable():
         assert (tiles[a:b] == t).all() and (a == 0 or tiles[a - 1] != t) and (b == len(k) or tiles[b] != t)
     empty = np.setdiff1d(np.arange(T), np.unique(tiles))
     assert (f["ranges"][empty] == 0).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The mask of near-threshold decisions (oracle/raster_oracle.c pixel_mask, O.fragile_pixels).  The strict GPU gradient
+# checks zero dL_dpix on it and then hold EVERY Gaussian to 1e-4 of scale; these tests pin what the mask means and that
+# masking cannot hide a scene: few pixels go, (almost) every graded Gaussian stays graded.
+MASK_MAX_SHARE_OF_BLENDED = 0.05
+MASK_MIN_GRADED_KEPT = 0.90
+_STATE = {}
+
+
+def _scene_state(name):
+    """(scene, oracle forward, mask, unmasked backward with mask) of a scene of scenes.ALL; dL_dpix from seed 123."""
+    if name not in _STATE:
+        _STATE.clear()                                    # (one scene at a time: many_tiles holds 4.5 M pixels)
+        s = scenes._scene(name)
+        f = O.forward(s)
+        dpix = np.random.default_rng(123).normal(size=(3, s["H"], s["W"])).astype(np.float32)
+        g = O.backward(s, f, dpix, pixel_mask=True)
+        _STATE[name] = (s, f, dpix, g)
+    return _STATE[name]
+
+
+def _walk_masks(s, f):
+    """Independent restatement, pixel by pixel in numpy: (mask [H, W], fragile [P], touched [P]) from ranges, point_list,
+    n_contrib, means2D and conic_opacity.  power in the oracle's fp32 operation order; exp taken in double and rounded (where
+    libm expf is correctly rounded that is the same number; a last-bit difference moves alpha x 255 by 6e-8 of a 1e-4 window)."""
+    W, H = s["W"], s["H"]
+    gx = (W + 15) // 16
+    m2, co = f["means2D"], f["conic_opacity"]
+    P = m2.shape[0]
+    mask, fragile, touched = np.zeros((H, W), bool), np.zeros(P, bool), np.zeros(P, bool)
+    half = np.float32(-0.5)
+    for py in range(H):
+        for px in range(W):
+            r0 = int(f["ranges"][(py // 16) * gx + px // 16, 0])
+            ids = f["point_list"][r0:r0 + int(f["n_contrib"][py, px])]
+            if ids.size == 0:
+                continue
+            dx, dy = m2[ids, 0] - np.float32(px), m2[ids, 1] - np.float32(py)
+            c = co[ids]
+            power = half * (c[:, 0] * dx * dx + c[:, 2] * dy * dy) - c[:, 1] * dx * dy
+            assert power.dtype == np.float32
+            G = np.exp(np.minimum(power, 0).astype(np.float64)).astype(np.float32)
+            alpha = np.minimum(np.float32(0.99), c[:, 3] * G)
+            p64, a64 = power.astype(np.float64), alpha.astype(np.float64)
+            near = np.where(power > 0, p64 < 1e-5, (np.abs(a64 * 255.0 - 1.0) < 1e-4) | (np.abs(p64) < 1e-5))
+            if near.any():
+                mask[py, px] = True
+                fragile[ids[near]] = True
+                touched[ids[(power <= 0) & (alpha >= np.float32(1.0) / np.float32(255.0))]] = True
+    return mask, fragile, touched | fragile
+
+
+@pytest.mark.parametrize("name", scenes.ALL)
+def test_fragile_pixel_mask_semantics(name):
+    s, f, dpix, g = _scene_state(name)
+    mask = g["fragile_pixels"]
+    assert mask.shape == (s["H"], s["W"]) and mask.dtype == bool
+    np.testing.assert_array_equal(O.fragile_pixels(s, f), mask)          # the convenience call; no dL_dpix involved
+    assert "fragile_pixels" not in O.backward(s, f, dpix)                # only when asked
+    assert not (g["fragile"] & ~g["touched"]).any()
+    assert mask.any() == g["fragile"].any()
+    assert not mask[f["n_contrib"] == 0].any()                            # a pixel that evaluates nothing decides nothing
+    if name in ("tiny_image", "sh1_M16", "strands_precomp"):
+        m_ref, fragile_ref, touched_ref = _walk_masks(s, f)
+        np.testing.assert_array_equal(mask, m_ref)
+        np.testing.assert_array_equal(g["fragile"], fragile_ref)
+        np.testing.assert_array_equal(g["touched"], touched_ref)
+    # linearity: every term a pixel contributes is linear in that pixel's dL_dpix, so the two halves add up to the whole --
+    # the same fp32 terms, summed in double in another order
+    g_out = O.backward(s, f, dpix * ~mask)
+    g_in = O.backward(s, f, dpix * mask)
+    scale = np.abs(g["acc"]).max(axis=0)
+    diff = np.abs(g_out["acc"] + g_in["acc"] - g["acc"]).max(axis=0) if g["acc"].size else scale
+    assert (diff <= 1e-10 * scale).all(), (diff, scale)
+    # a Gaussian that is not touched gets nothing from the masked pixels
+    assert not g_in["acc"][~g["touched"]].any()
+
+
+@pytest.mark.parametrize("name", scenes.ALL)
+def test_fragile_pixel_mask_hides_nothing(name):
+    """The conditions under which zeroing dL_dpix on the mask leaves a check of the whole scene: at most 5 % of the blended
+    pixels masked (one_huge_tile blends 8 pixels: at most 1), at least 90 % of the Gaussians with a gradient keep one.
+    Measured: worst 2.15 % (dense_long_lists) and 96.8 % (one_huge_tile).  A scene added to scenes.ALL must meet them too."""
+    s, f, dpix, g = _scene_state(name)
+    mask = g["fragile_pixels"]
+    blended = f["n_contrib"] > 0
+    g_m = O.backward(s, f, dpix * ~mask)
+    graded = np.abs(g["acc"]).max(axis=1) > 0
+    kept = graded & (np.abs(g_m["acc"]).max(axis=1) > 0)
+    print(f"MASK {name}: masked {int(mask.sum())} of {int(blended.sum())} blended pixels ({mask.size} pixels), graded "
+          f"{int(graded.sum())}, still graded {int(kept.sum())}, fragile {int(g['fragile'].sum())}, touched {int(g['touched'].sum())}")
+    if name == "one_huge_tile":
+        assert int(mask.sum()) <= 1
+    else:
+        assert int(mask.sum()) <= MASK_MAX_SHARE_OF_BLENDED * int(blended.sum())
+    assert int(kept.sum()) >= MASK_MIN_GRADED_KEPT * int(graded.sum())
+    if name != "all_culled":
+        assert graded.any() and blended.any()
