@@ -109,6 +109,23 @@ static int check_aligned(const void* p, const char* what) {
   return 0;
 }
 
+int hgs_param_forward_check(int P, const HgsParamForward* pf, bool one_launch, const char* who) {
+  if (!pf || (pf->kind != HGS_PARAMS_HAIR && pf->kind != HGS_PARAMS_CLOUD)) {
+    hgs_set_error("%s: HgsParamForward.kind must be HGS_PARAMS_HAIR or HGS_PARAMS_CLOUD", who);
+    return 1;
+  }
+  const bool hair = pf->kind == HGS_PARAMS_HAIR;
+  const bool null = hair ? (!pf->endpoints || !pf->endpoint_pairs || !pf->width || !pf->means3D)
+                         : (!pf->scaling_raw || !pf->rotation_raw || (one_launch && !pf->means3D));
+  const bool unaligned = one_launch && ((!hair && ((size_t)pf->rotation_raw & 15)) || ((size_t)pf->quat & 15) || ((size_t)pf->extra4 & 15));
+  if (P > 0 && (null || !pf->opacity_raw || !pf->mask_raw || !pf->scale || !pf->quat || !pf->opacity || !pf->extra4 || unaligned)) {
+    hgs_set_error(one_launch ? "%s: null (or, rotation_raw / quat / extra4, not 16-byte aligned) field of HgsParamForward"
+                             : "%s: null field of HgsParamForward", who);
+    return 1;
+  }
+  return 0;
+}
+
 extern "C" {
 
 int hgs_abi_version(void) { return HGS_ABI_VERSION; }
@@ -142,18 +159,13 @@ int hgs_image_layout(int W, int H, size_t* offsets) { HgsImage im; hgs_image_car
 int hgs_binning_layout(int R, size_t* offsets) { HgsBinning b; hgs_binning_carve(nullptr, (size_t)R, b, offsets); return 0; }
 
 static_assert(HGS_FUSED_PREPROCESS_MAX_TILES == HGS_FUSED_SCAN_MAX_T, "include/hgs.h states the scatter kernel's scan limit");
-// the strand parameters of hgs_hair_forward_preprocess (NULL: the Gaussians are given)
-struct HairSrc {
-  const float* endpoints; const long long* pairs; const float* width; float f; const float* opacity_raw; const float* mask_raw;
-  float* xyz; float* scale; float* quat; float* opacity; float* extra4; const HgsStrandFusion* fusion;
-  const float* scaling_raw; const float* rotation_raw;    // != NULL: a Stage-I cloud (hgs_cloud_forward_preprocess)
-};
 static int forward_preprocess_impl(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
                                    const float* colors_precomp, const float* opacities, const float* scales,
                                    float scale_modifier, const float* rotations, const float* cov3D_precomp,
                                    const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
                                    float tan_fovy, int prefiltered, void* geom_buf, void* image_buf, int* radii,
-                                   int* num_rendered_host, unsigned int* max_rendered, const HairSrc* hair);
+                                   int* num_rendered_host, unsigned int* max_rendered, const HgsParamForward* params,
+                                   const HgsStrandFusion* fusion);
 
 int hgs_forward_preprocess(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
                            const float* colors_precomp, const float* opacities, const float* scales,
@@ -163,45 +175,18 @@ int hgs_forward_preprocess(void* stream, int P, int D, int M, int W, int H, cons
                            int* num_rendered_host, unsigned int* max_rendered) {
   return forward_preprocess_impl(stream, P, D, M, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
                                  rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, prefiltered,
-                                 geom_buf, image_buf, radii, num_rendered_host, max_rendered, nullptr);
+                                 geom_buf, image_buf, radii, num_rendered_host, max_rendered, nullptr, nullptr);
 }
 
-int hgs_hair_forward_preprocess(void* stream, int P, int D, int M, int W, int H, const float* endpoints,
-                                const long long* endpoint_pairs, const float* width, float dist_to_scale_factor,
-                                const float* opacity_raw, const float* mask_raw, const float* shs, float* xyz, float* scale,
-                                float* quat, float* opacity, float* extra4, const float* viewmatrix, const float* projmatrix,
-                                const float* campos, float tan_fovx, float tan_fovy, int flags, void* geom_buf,
-                                void* image_buf, int* radii, unsigned int* max_rendered, const HgsStrandFusion* fusion) {
-  if (P > 0 && (!endpoints || !endpoint_pairs || !width || !opacity_raw || !mask_raw || !xyz || !scale || !quat || !opacity ||
-                !extra4 || ((size_t)quat & 15) || ((size_t)extra4 & 15))) {
-    hgs_set_error("hgs_hair_forward_preprocess: null (or, quat / extra4, not 16-byte aligned) argument");
-    return 1;
-  }
-  if (!max_rendered) { hgs_set_error("hgs_hair_forward_preprocess: capacity mode only (max_rendered must be given)"); return 1; }
-  const HairSrc hair = {endpoints, endpoint_pairs, width, dist_to_scale_factor, opacity_raw, mask_raw, xyz, scale, quat, opacity,
-                        extra4, fusion, nullptr, nullptr};
-  return forward_preprocess_impl(stream, P, D, M, W, H, xyz, shs, nullptr, opacity, scale, 1.f, quat, nullptr, viewmatrix,
-                                 projmatrix, campos, tan_fovx, tan_fovy, flags, geom_buf, image_buf, radii, nullptr,
-                                 max_rendered, &hair);
-}
-
-int hgs_cloud_forward_preprocess(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* scaling_raw,
-                                 const float* rotation_raw, const float* opacity_raw, const float* mask_raw, const float* shs,
-                                 float* scale, float* quat, float* opacity, float* extra4, const float* viewmatrix,
-                                 const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, int flags,
-                                 void* geom_buf, void* image_buf, int* radii, unsigned int* max_rendered,
-                                 const HgsStrandFusion* fusion) {
-  if (P > 0 && (!means3D || !scaling_raw || !rotation_raw || !opacity_raw || !mask_raw || !scale || !quat || !opacity || !extra4 ||
-                ((size_t)rotation_raw & 15) || ((size_t)quat & 15) || ((size_t)extra4 & 15))) {
-    hgs_set_error("hgs_cloud_forward_preprocess: null (or, rotation_raw / quat / extra4, not 16-byte aligned) argument");
-    return 1;
-  }
-  if (!max_rendered) { hgs_set_error("hgs_cloud_forward_preprocess: capacity mode only (max_rendered must be given)"); return 1; }
-  const HairSrc cloud = {nullptr, nullptr, nullptr, 0.f, opacity_raw, mask_raw, nullptr, scale, quat, opacity, extra4, fusion,
-                         scaling_raw, rotation_raw};
-  return forward_preprocess_impl(stream, P, D, M, W, H, means3D, shs, nullptr, opacity, scale, 1.f, quat, nullptr, viewmatrix,
-                                 projmatrix, campos, tan_fovx, tan_fovy, flags, geom_buf, image_buf, radii, nullptr,
-                                 max_rendered, &cloud);
+int hgs_params_forward_preprocess(void* stream, int P, int D, int M, int W, int H, const HgsParamForward* pf, const float* shs,
+                                  const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                                  float tan_fovy, int flags, void* geom_buf, void* image_buf, int* radii,
+                                  unsigned int* max_rendered, const HgsStrandFusion* fusion) {
+  if (hgs_param_forward_check(P, pf, true, "hgs_params_forward_preprocess")) return 1;
+  if (!max_rendered) { hgs_set_error("hgs_params_forward_preprocess: capacity mode only (max_rendered must be given)"); return 1; }
+  return forward_preprocess_impl(stream, P, D, M, W, H, pf->means3D, shs, nullptr, pf->opacity, pf->scale, 1.f, pf->quat, nullptr,
+                                 viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, flags, geom_buf, image_buf, radii, nullptr,
+                                 max_rendered, pf, fusion);
 }
 
 static int forward_preprocess_impl(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
@@ -209,7 +194,8 @@ static int forward_preprocess_impl(void* stream, int P, int D, int M, int W, int
                                    float scale_modifier, const float* rotations, const float* cov3D_precomp,
                                    const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
                                    float tan_fovy, int prefiltered, void* geom_buf, void* image_buf, int* radii,
-                                   int* num_rendered_host, unsigned int* max_rendered, const HairSrc* hair) {
+                                   int* num_rendered_host, unsigned int* max_rendered, const HgsParamForward* params,
+                                   const HgsStrandFusion* fusion) {
   hipStream_t s = (hipStream_t)stream;
   if (P < 0 || W <= 0 || H <= 0) { hgs_set_error("bad sizes P=%d W=%d H=%d", P, W, H); return 1; }
   if ((size_t)((W + HGS_TILE - 1) / HGS_TILE) * ((H + HGS_TILE - 1) / HGS_TILE) > HGS_MAX_TILES) { hgs_set_error("%dx%d: more than 2^24 tiles", W, H); return 1; }
@@ -221,14 +207,14 @@ static int forward_preprocess_impl(void* stream, int P, int D, int M, int W, int
   const int T = ((W + HGS_TILE - 1) / HGS_TILE) * ((H + HGS_TILE - 1) / HGS_TILE);
   if (!(prefiltered & HGS_IMAGE_PREZEROED) &&
       hgs_zero_async(s, im.tile_count, hgs_image_zero_words((size_t)T) * sizeof(uint32_t))) return 1;
-  const HgsPrologue* rider = (hair && hair->fusion && hair->fusion->prologue.table) ? &hair->fusion->prologue : nullptr;
+  const HgsPrologue* rider = (params && fusion && fusion->prologue.table) ? &fusion->prologue : nullptr;
   if (rider && (!rider->slot || rider->view < 0 || ((size_t)rider->zero_ptr & 3) || (rider->zero_bytes & 3) ||
                 (rider->zero_bytes && !rider->zero_ptr))) {
-    hgs_set_error("hgs_hair/cloud_forward_preprocess: bad prologue group");
+    hgs_set_error("hgs_params_forward_preprocess: bad prologue group");
     return 1;
   }
-  if (hair && T > HGS_FUSED_SCAN_MAX_T) {
-    hgs_set_error("hgs_hair_forward_preprocess: %d tiles, at most %d (the tile counters are cleared by the scatter kernel's scan)", T, HGS_FUSED_SCAN_MAX_T);
+  if (params && T > HGS_FUSED_SCAN_MAX_T) {
+    hgs_set_error("hgs_params_forward_preprocess: %d tiles, at most %d (the tile counters are cleared by the scatter kernel's scan)", T, HGS_FUSED_SCAN_MAX_T);
     return 1;
   }
   if (P == 0 && rider &&     // nothing to ride on: the prologue as a launch of its own
@@ -264,16 +250,11 @@ static int forward_preprocess_impl(void* stream, int P, int D, int M, int W, int
   // the one-workgroup scan kernel in between.)
   const bool fused_scan = !num_rendered_host && max_rendered && T <= HGS_FUSED_SCAN_MAX_T && P <= HGS_FUSED_SCAN_MAX_P;
   a.fused_scan_ptr = fused_scan ? (unsigned long long)(size_t)max_rendered : 0ull;
-  if (hair) {
-    if (!fused_scan) { hgs_set_error("hgs_hair_forward_preprocess: the scan must be the scatter kernel's (sizes beyond its limits)"); return 1; }
-    HgsStrandFusion fu = hair->fusion ? *hair->fusion : HgsStrandFusion{};
+  if (params) {
+    if (!fused_scan) { hgs_set_error("hgs_params_forward_preprocess: the scan must be the scatter kernel's (sizes beyond its limits)"); return 1; }
+    HgsStrandFusion fu = fusion ? *fusion : HgsStrandFusion{};
     if (!(fu.smooth_pairs && fu.n_smooth > 0 && fu.smooth_partials)) fu.n_smooth = 0;
-    if (hair->scaling_raw) {
-      if (hgs_launch_cloud_preprocess_fwd(s, a, g, im, radii, hair->scaling_raw, hair->rotation_raw, hair->opacity_raw,
-                                          hair->mask_raw, hair->scale, hair->quat, hair->opacity, hair->extra4, fu.prologue)) return 1;
-    } else if (hgs_launch_hair_preprocess_fwd(s, a, g, im, radii, hair->endpoints, hair->pairs, hair->width, hair->f,
-                                              hair->opacity_raw, hair->mask_raw, hair->xyz, hair->scale, hair->quat,
-                                              hair->opacity, hair->extra4, fu)) return 1;
+    if (hgs_launch_param_preprocess_fwd(s, a, g, im, radii, *params, fu)) return 1;
   } else if (hgs_launch_preprocess_fwd(s, a, g, im, radii)) return 1;
   if (!fused_scan && hgs_launch_scan(s, P, T, g, im, max_rendered, a.row_runs)) return 1;
   if (num_rendered_host) {
@@ -379,6 +360,7 @@ static int backward_impl(void* stream, int P, int D, int M, int R, int W, int H,
   return hgs_launch_preprocess_bwd(s, a, g, b, inst_grad, R, im.status, pb);
 }
 
+size_t hgs_param_forward_bytes(void) { return sizeof(HgsParamForward); }
 size_t hgs_param_backward_bytes(void) { return sizeof(HgsParamBackward); }
 size_t hgs_adam_prep_bytes(void) { return sizeof(HgsAdamPrep); }
 size_t hgs_adam_inline_bytes(void) { return sizeof(HgsAdamInline); }

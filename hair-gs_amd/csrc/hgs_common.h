@@ -317,15 +317,11 @@ struct HgsFwdArgs {
 #endif
 #define HGS_FUSED_SCAN_MAX_T 8192    // tiles the scatter kernel's scan workgroups take (a share's offsets live in the block's tile table); 1080p has 8160
 int hgs_launch_preprocess_fwd(hipStream_t s, const HgsFwdArgs& a, const HgsGeom& g, const HgsImage& im, int* radii);
-// strand parameters -> Gaussians -> preprocess in one launch (hgs_hair_forward_preprocess), riders of `fusion` included
-int hgs_launch_hair_preprocess_fwd(hipStream_t s, const HgsFwdArgs& a, const HgsGeom& g, const HgsImage& im, int* radii,
-                                   const float* endpoints, const long long* pairs, const float* width, float f,
-                                   const float* opacity_raw, const float* mask_raw, float* xyz, float* scale, float* quat,
-                                   float* opacity, float* extra4, const HgsStrandFusion& fusion);
-int hgs_launch_cloud_preprocess_fwd(hipStream_t s, const HgsFwdArgs& a, const HgsGeom& g, const HgsImage& im, int* radii,
-                                    const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
-                                    const float* mask_raw, float* scale, float* quat, float* opacity, float* extra4,
-                                    const HgsPrologue& pro);
+// raw parameters -> Gaussians -> preprocess in one launch (hgs_params_forward_preprocess; kernel by pf.kind), riders of `fusion` included
+int hgs_launch_param_preprocess_fwd(hipStream_t s, const HgsFwdArgs& a, const HgsGeom& g, const HgsImage& im, int* radii,
+                                    const HgsParamForward& pf, const HgsStrandFusion& fusion);
+// pf and its kind, and for P > 0 the kind's pointers (one_launch: also a cloud's means3D and the 16-byte alignments); 1 = error set
+int hgs_param_forward_check(int P, const HgsParamForward* pf, bool one_launch, const char* who);
 int hgs_launch_scan(hipStream_t s, int P, int T, const HgsGeom& g, const HgsImage& im, unsigned int* max_rendered, int row_runs = 0);
 int hgs_launch_scatter(hipStream_t s, int P, int W, int H, int Rcap, const float* features, const float* extra, int n_extra,
                        const HgsGeom& g, const HgsImage& im, const HgsBinning& b);

@@ -141,8 +141,8 @@ template <int LOG> __device__ __forceinline__ int th_find(const TileHashT<LOG>& 
 }
 
 // ------------------------------------------------------------------------------------------------
-// The model's raw parameters, for the kernels that derive a lane's Gaussian themselves (hgs_hair_forward_preprocess /
-// hgs_cloud_forward_preprocess): inputs, and the arrays the derived Gaussians are written to (the backward and the scatter
+// The model's raw parameters, for the kernels that derive a lane's Gaussian themselves (hgs_params_forward_preprocess;
+// filled from the caller's HgsParamForward by hgs_launch_param_preprocess_fwd): inputs, and the arrays the derived Gaussians are written to (the backward and the scatter
 // kernel read them).
 struct HgsParamSrc {
   const float* ep; const long long* pairs; const float* width; float f;        // strands
@@ -480,7 +480,7 @@ __global__ __launch_bounds__(HGS_BLOCK) void preprocess_fwd_kernel(HgsFwdArgs a,
   preprocess_fwd_body<SRC_GIVEN>(a, g, im, radii, HgsParamSrc{}, red, th);
 }
 
-// The iteration's FIRST launch for a strand model (hgs_hair_forward_preprocess): strand parameters -> Gaussians -> preprocess in
+// The iteration's FIRST launch for a strand model (hgs_params_forward_preprocess, HGS_PARAMS_HAIR): strand parameters -> Gaussians -> preprocess in
 // one kernel, with the riders the parameter kernel used to carry (include/hgs.h HgsStrandFusion: smoothness partial sums;
 // HgsPrologue: view select + clearing of the image buffer's counters -- `pro` stays the LAST argument, where the graph functions
 // find it).  Two things differ from the two-launch form because the riders now run BESIDE the preprocess workgroups:
@@ -510,7 +510,7 @@ __global__ __launch_bounds__(HGS_BLOCK) void hair_preprocess_fwd_kernel(HgsFwdAr
   preprocess_fwd_body<SRC_STRAND>(a, g, im, radii, st, red, th);
 }
 
-// The same for the Stage-I cloud (hgs_cloud_forward_preprocess: cloud_fwd_kernel + preprocess_fwd_kernel; no smoothness term)
+// The same for the Stage-I cloud (HGS_PARAMS_CLOUD: cloud_fwd_kernel + preprocess_fwd_kernel; no smoothness term)
 __global__ __launch_bounds__(HGS_BLOCK) void cloud_preprocess_fwd_kernel(HgsFwdArgs a, HgsGeom g, HgsImage im, int* radii,
                                                                          HgsParamSrc st, HgsPrologue pro) {
   __shared__ uint32_t red[4];
@@ -1501,33 +1501,24 @@ bool hgs_preprocess_prologue_kernel(const void* func, int* n_params) {
   if (func == (const void*)cloud_preprocess_fwd_kernel) { *n_params = 6; return true; }
   return false;
 }
-int hgs_launch_hair_preprocess_fwd(hipStream_t s, const HgsFwdArgs& a, const HgsGeom& g, const HgsImage& im, int* radii,
-                                   const float* endpoints, const long long* pairs, const float* width, float f,
-                                   const float* opacity_raw, const float* mask_raw, float* xyz, float* scale, float* quat,
-                                   float* opacity, float* extra4, const HgsStrandFusion& fusion) {
+int hgs_launch_param_preprocess_fwd(hipStream_t s, const HgsFwdArgs& a, const HgsGeom& g, const HgsImage& im, int* radii,
+                                    const HgsParamForward& pf, const HgsStrandFusion& fusion) {
+  const bool cloud = pf.kind == HGS_PARAMS_CLOUD;
   HgsStrandFusion fu = fusion;
   const HgsPrologue pro = fu.prologue;
   fu.prologue = HgsPrologue{};      // (handed over as the kernel's last argument)
-  const HgsParamSrc st = {endpoints, pairs, width, f, nullptr, nullptr, opacity_raw, mask_raw, xyz, scale, quat, opacity, extra4};
+  if (cloud) fu.n_smooth = 0;       // (a cloud has no smoothness term: only the prologue group is used)
+  const HgsParamSrc st = {pf.endpoints, pf.endpoint_pairs, pf.width, pf.dist_to_scale_factor, pf.scaling_raw, pf.rotation_raw,
+                          pf.opacity_raw, pf.mask_raw, cloud ? nullptr : pf.means3D, pf.scale, pf.quat, pf.opacity, pf.extra4};
   const unsigned nblk = (unsigned)((a.P + HGS_BLOCK - 1) / HGS_BLOCK) + (unsigned)((fu.n_smooth + 255) / 256) +
                         (pro.table ? hgs_prologue_blocks(pro.zero_bytes / 4) : 0u);
   {
     HgsProfScope _prof(s, HGS_K_PREPROCESS_FWD);
-    hipLaunchKernelGGL(hair_preprocess_fwd_kernel, dim3(nblk), dim3(HGS_BLOCK), 0, s, a, g, im, radii, st, fu, pro);
-  }
-  HGS_CHECK_LAUNCH();
-  return 0;
-}
-int hgs_launch_cloud_preprocess_fwd(hipStream_t s, const HgsFwdArgs& a, const HgsGeom& g, const HgsImage& im, int* radii,
-                                    const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
-                                    const float* mask_raw, float* scale, float* quat, float* opacity, float* extra4,
-                                    const HgsPrologue& pro) {
-  const HgsParamSrc st = {nullptr, nullptr, nullptr, 0.f, scaling_raw, rotation_raw, opacity_raw, mask_raw, nullptr, scale, quat,
-                          opacity, extra4};
-  const unsigned nblk = (unsigned)((a.P + HGS_BLOCK - 1) / HGS_BLOCK) + (pro.table ? hgs_prologue_blocks(pro.zero_bytes / 4) : 0u);
-  {
-    HgsProfScope _prof(s, HGS_K_PREPROCESS_FWD);
-    hipLaunchKernelGGL(cloud_preprocess_fwd_kernel, dim3(nblk), dim3(HGS_BLOCK), 0, s, a, g, im, radii, st, pro);
+    if (cloud) {
+      hipLaunchKernelGGL(cloud_preprocess_fwd_kernel, dim3(nblk), dim3(HGS_BLOCK), 0, s, a, g, im, radii, st, pro);
+    } else {
+      hipLaunchKernelGGL(hair_preprocess_fwd_kernel, dim3(nblk), dim3(HGS_BLOCK), 0, s, a, g, im, radii, st, fu, pro);
+    }
   }
   HGS_CHECK_LAUNCH();
   return 0;

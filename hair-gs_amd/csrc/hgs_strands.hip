@@ -161,27 +161,26 @@ int hgs_strand_geometry_backward(void* stream, int P, int E, const float* endpoi
   return 0;
 }
 
-int hgs_hair_params_forward(void* stream, int P, const float* endpoints, const long long* endpoint_pairs,
-                            const float* width, float dist_to_scale_factor, const float* opacity_raw,
-                            const float* mask_raw, float* xyz, float* scale, float* quat, float* dir, float* opacity,
-                            float* extra4, const HgsStrandFusion* fusion) {
+int hgs_params_forward(void* stream, int P, const HgsParamForward* pf, const HgsStrandFusion* fusion) {
+  if (hgs_param_forward_check(P, pf, false, "hgs_params_forward")) return 1;
   HgsStrandFusion fu = fusion ? *fusion : HgsStrandFusion{};
-  if (prologue_rider(stream, P, fu.prologue, "hgs_hair_params_forward")) return 1;
+  if (prologue_rider(stream, P, fu.prologue, "hgs_params_forward")) return 1;
   if (P == 0) return 0;
-  const bool smooth = fu.smooth_pairs && fu.n_smooth > 0 && fu.smooth_partials;
+  const bool smooth = pf->kind == HGS_PARAMS_HAIR && fu.smooth_pairs && fu.n_smooth > 0 && fu.smooth_partials;
   if (!smooth) fu.n_smooth = 0;
-  if (!endpoints || !endpoint_pairs || !width || !opacity_raw || !mask_raw || !xyz || !scale || !quat || !opacity || !extra4) {
-    hgs_set_error("hgs_hair_params_forward: null argument");
-    return 1;
-  }
   hipStream_t s = (hipStream_t)stream;
   {
     HgsProfScope _prof(s, HGS_K_STRAND_FWD);
     const HgsPrologue pro = fu.prologue;
     fu.prologue = HgsPrologue{};     // (handed over as the kernel's last argument, where the graph functions find it)
-    hipLaunchKernelGGL(strand_fwd_kernel, dim3((P + 255) / 256 + (fu.n_smooth + 255) / 256 + rider_blocks(pro)), dim3(256), 0, s, P,
-                       endpoints, endpoint_pairs, width, dist_to_scale_factor, xyz, scale, quat, dir, opacity_raw, mask_raw,
-                       opacity, extra4, fu, pro);
+    if (pf->kind == HGS_PARAMS_CLOUD) {
+      hipLaunchKernelGGL(cloud_fwd_kernel, dim3((P + 255) / 256 + rider_blocks(pro)), dim3(256), 0, s, P, pf->scaling_raw,
+                         pf->rotation_raw, pf->opacity_raw, pf->mask_raw, pf->scale, pf->quat, pf->opacity, pf->extra4, pro);
+    } else {
+      hipLaunchKernelGGL(strand_fwd_kernel, dim3((P + 255) / 256 + (fu.n_smooth + 255) / 256 + rider_blocks(pro)), dim3(256), 0, s, P,
+                         pf->endpoints, pf->endpoint_pairs, pf->width, pf->dist_to_scale_factor, pf->means3D, pf->scale, pf->quat,
+                         (float*)nullptr, pf->opacity_raw, pf->mask_raw, pf->opacity, pf->extra4, fu, pro);
+    }
   }
   HGS_CHECK_LAUNCH();
   return 0;
@@ -252,26 +251,6 @@ int hgs_hair_endpoint_gather(void* stream, int E, const float* seg_contrib, cons
       return 1;
     }
     hipLaunchKernelGGL(strand_gather_kernel, dim3((E + 255) / 256 + (fu.head_tail.out ? 1 : 0)), dim3(256), 0, s, A);
-  }
-  HGS_CHECK_LAUNCH();
-  return 0;
-}
-
-int hgs_cloud_params_forward(void* stream, int P, const float* scaling_raw, const float* rotation_raw,
-                             const float* opacity_raw, const float* mask_raw, float* scale, float* quat, float* opacity,
-                             float* extra4, const HgsStrandFusion* fusion) {
-  const HgsPrologue pro = fusion ? fusion->prologue : HgsPrologue{};
-  if (prologue_rider(stream, P, pro, "hgs_cloud_params_forward")) return 1;
-  if (P == 0) return 0;
-  if (!scaling_raw || !rotation_raw || !opacity_raw || !mask_raw || !scale || !quat || !opacity || !extra4) {
-    hgs_set_error("hgs_cloud_params_forward: null argument");
-    return 1;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  {
-    HgsProfScope _prof(s, HGS_K_STRAND_FWD);
-    hipLaunchKernelGGL(cloud_fwd_kernel, dim3((P + 255) / 256 + rider_blocks(pro)), dim3(256), 0, s, P, scaling_raw, rotation_raw,
-                       opacity_raw, mask_raw, scale, quat, opacity, extra4, pro);
   }
   HGS_CHECK_LAUNCH();
   return 0;

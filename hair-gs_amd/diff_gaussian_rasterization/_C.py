@@ -187,33 +187,42 @@ def rasterize_gaussians_multi(background7, means3D, colors, extra4, opacity, sca
                     extra4, True, image_buffer, None, hair)
 
 
-class HairSource:
-    """The strand parameters behind means3D / scales / rotations / opacity (/ extra4) of a pass: those five tensors are then
-    OUTPUTS, written by the pass's first launch.  In capacity mode that launch is hgs_hair_forward_preprocess (parameters ->
-    Gaussians -> preprocess in one kernel, `fusion`'s riders beside it); otherwise hgs_hair_params_forward runs in front of
-    the ordinary preprocess launch.  `fusion`: hgs_runtime.StrandFusion (or None); `fill(fused)` is called once the form is
-    known and must put the iteration prologue (if one rides) into `fusion` with the matching zero range."""
+class _ParamSource:
+    """The model's raw parameters behind means3D / scales / rotations / opacity (/ extra4) of a pass: those tensors are then
+    OUTPUTS (a cloud's means3D: its own parameter), written by the pass's first launch.  In capacity mode that launch is
+    hgs_params_forward_preprocess (parameters -> Gaussians -> preprocess in one kernel, `fusion`'s riders beside it); otherwise, or
+    with fuse=False, hgs_params_forward runs in front of the ordinary preprocess launch.  `fusion`: hgs_runtime.StrandFusion (or
+    None); `fill(fused)` is called once the form is known and must put the iteration prologue (if one rides) into `fusion` with
+    the matching zero range (hgs_runtime.strand_step.ViewTable.carry_prologue).
+    Holds `params`, an hgs_runtime.ParamForward filled in except for the output pointers, and `inputs`, the validated
+    contiguous tensors it points to."""
 
-    kind = "hair"
+    def __init__(self, kind, fusion, fill, fuse, **inputs):
+        self.params, self.fusion, self.fill, self.fuse = rt.ParamForward(kind=kind), fusion, fill, bool(fuse)
+        self.inputs = {k: rt.require_gpu_tensor(t, k, torch.int64) if k == "endpoint_pairs" else _f32(t, k) for k, t in inputs.items()}
+        for k, t in self.inputs.items():
+            setattr(self.params, k, rt.ptr(t))
 
-    def __init__(self, endpoints, pairs, width, factor, opacity_raw, mask_raw, fusion=None, fill=None):
-        self.endpoints, self.pairs, self.width, self.factor = endpoints, pairs, width, float(factor)
-        self.opacity_raw, self.mask_raw, self.fusion, self.fill = opacity_raw, mask_raw, fusion, fill
+
+class HairSource(_ParamSource):
+    """The strand parameters of a pass (include/hgs.h HGS_PARAMS_HAIR)."""
+
+    def __init__(self, endpoints, pairs, width, factor, opacity_raw, mask_raw, fusion=None, fill=None, fuse=True):
+        super().__init__(rt.PARAMS_HAIR, fusion, fill, fuse, endpoints=endpoints, endpoint_pairs=pairs, width=width,
+                         opacity_raw=opacity_raw, mask_raw=mask_raw)
+        self.params.dist_to_scale_factor = float(factor)
 
 
-class CloudSource:
-    """The Stage-I counterpart of HairSource: the raw scaling / rotation / opacity / mask parameters behind scales / rotations /
-    opacity / extra4 of a pass (means3D is the model's own parameter): hgs_cloud_forward_preprocess in capacity mode,
-    hgs_cloud_params_forward in front of the ordinary preprocess launch otherwise."""
-    kind = "cloud"
+class CloudSource(_ParamSource):
+    """The Stage-I counterpart: a cloud's raw scaling / rotation / opacity / mask parameters (HGS_PARAMS_CLOUD)."""
 
-    def __init__(self, scaling_raw, rotation_raw, opacity_raw, mask_raw, fusion=None, fill=None):
-        self.scaling_raw, self.rotation_raw = scaling_raw, rotation_raw
-        self.opacity_raw, self.mask_raw, self.fusion, self.fill = opacity_raw, mask_raw, fusion, fill
+    def __init__(self, scaling_raw, rotation_raw, opacity_raw, mask_raw, fusion=None, fill=None, fuse=True):
+        super().__init__(rt.PARAMS_CLOUD, fusion, fill, fuse, scaling_raw=scaling_raw, rotation_raw=rotation_raw,
+                         opacity_raw=opacity_raw, mask_raw=mask_raw)
 
 
 def will_fuse_hair(W, H):
-    """Would a pass with a HairSource at this size run the one-launch form now?  (capacity mode with a learnt capacity,
+    """Would a pass with a HairSource / CloudSource (fuse=True) at this size run the one-launch form now?  (capacity mode with a learnt capacity,
     at most HGS_FUSED_PREPROCESS_MAX_TILES tiles)"""
     return (_state["async"] and _state["cap"] > 0 and os.environ.get("HGS_FUSE_PREPROCESS", "1") != "0"
             and ((int(W) + 15) // 16) * ((int(H) + 15) // 16) <= rt.FUSED_PREPROCESS_MAX_TILES)
@@ -264,48 +273,30 @@ def _forward(background, means3D, colors, opacity, scales, rotations, scale_modi
         use_async = _state["async"] and _state["cap"] > 0 and P > 0
         flags |= _row_runs_flag(P, use_async)
         n_host = C.c_int(0)
-        fused_hair = hair is not None and use_async and will_fuse_hair(W, H)
+        fused_hair = hair is not None and hair.fuse and use_async and will_fuse_hair(W, H)
+        mr_ = rt.ptr(max_rendered if max_rendered is not None else _max_rendered(dev)) if use_async else None
         if hair is not None:
             if scale_modifier != 1.0 or colors_ is not None or cov_ is not None or sh_ is None:
-                raise RuntimeError("a HairSource pass renders SH colours at scale_modifier 1")
+                raise RuntimeError("a HairSource / CloudSource pass renders SH colours at scale_modifier 1")
             if hair.fill is not None:
                 hair.fill(fused_hair)
-            o_raw, m_raw = _f32(hair.opacity_raw, "opacity_raw"), _f32(hair.mask_raw, "mask_raw")
-            fu_ = None if hair.fusion is None else C.byref(hair.fusion)
             ex_out = extra_ if extra_ is not None else torch.empty((P, 4), dtype=torch.float32, device=dev)
-            mr_ = rt.ptr(max_rendered if max_rendered is not None else _max_rendered(dev)) if fused_hair else None
-            if hair.kind == "hair":
-                ep_, w_ = _f32(hair.endpoints, "endpoints"), _f32(hair.width, "width")
-                pairs_ = rt.require_gpu_tensor(hair.pairs, "endpoint_pairs", torch.int64)
-                if fused_hair:
-                    rt.check(L.hgs_hair_forward_preprocess(stream, P, int(degree), M, W, H, rt.ptr(ep_), rt.ptr(pairs_), rt.ptr(w_),
-                                                           hair.factor, rt.ptr(o_raw), rt.ptr(m_raw), rt.ptr(sh_), rt.ptr(means3D),
-                                                           rt.ptr(scales_), rt.ptr(rots_), rt.ptr(opacity_), rt.ptr(ex_out),
-                                                           rt.ptr(view), rt.ptr(proj), rt.ptr(cam), float(tan_fovx),
-                                                           float(tan_fovy), flags, rt.ptr(geom), rt.ptr(img), rt.ptr(radii), mr_, fu_))
-                else:
-                    rt.check(L.hgs_hair_params_forward(stream, P, rt.ptr(ep_), rt.ptr(pairs_), rt.ptr(w_), hair.factor, rt.ptr(o_raw),
-                                                       rt.ptr(m_raw), rt.ptr(means3D), rt.ptr(scales_), rt.ptr(rots_), None,
-                                                       rt.ptr(opacity_), rt.ptr(ex_out), fu_))
+            pf = hair.params
+            pf.means3D, pf.scale, pf.quat, pf.opacity, pf.extra4 = (rt.ptr(means3D), rt.ptr(scales_), rt.ptr(rots_),
+                                                                    rt.ptr(opacity_), rt.ptr(ex_out))
+            fu_ = None if hair.fusion is None else C.byref(hair.fusion)
+            if fused_hair:
+                rt.check(L.hgs_params_forward_preprocess(stream, P, int(degree), M, W, H, C.byref(pf), rt.ptr(sh_), rt.ptr(view),
+                                                         rt.ptr(proj), rt.ptr(cam), float(tan_fovx), float(tan_fovy), flags,
+                                                         rt.ptr(geom), rt.ptr(img), rt.ptr(radii), mr_, fu_))
             else:
-                s_raw, r_raw = _f32(hair.scaling_raw, "scaling_raw"), _f32(hair.rotation_raw, "rotation_raw")
-                if fused_hair:
-                    rt.check(L.hgs_cloud_forward_preprocess(stream, P, int(degree), M, W, H, rt.ptr(means3D), rt.ptr(s_raw),
-                                                            rt.ptr(r_raw), rt.ptr(o_raw), rt.ptr(m_raw), rt.ptr(sh_),
-                                                            rt.ptr(scales_), rt.ptr(rots_), rt.ptr(opacity_), rt.ptr(ex_out),
-                                                            rt.ptr(view), rt.ptr(proj), rt.ptr(cam), float(tan_fovx),
-                                                            float(tan_fovy), flags, rt.ptr(geom), rt.ptr(img), rt.ptr(radii), mr_, fu_))
-                else:
-                    rt.check(L.hgs_cloud_params_forward(stream, P, rt.ptr(s_raw), rt.ptr(r_raw), rt.ptr(o_raw), rt.ptr(m_raw),
-                                                        rt.ptr(scales_), rt.ptr(rots_), rt.ptr(opacity_), rt.ptr(ex_out), fu_))
+                rt.check(L.hgs_params_forward(stream, P, C.byref(pf), fu_))
         if not fused_hair:
             rt.check(L.hgs_forward_preprocess(stream, P, int(degree), M, W, H, rt.ptr(means3D), rt.ptr(sh_), rt.ptr(colors_),
                                               rt.ptr(opacity_), rt.ptr(scales_), float(scale_modifier), rt.ptr(rots_),
                                               rt.ptr(cov_), rt.ptr(view), rt.ptr(proj), rt.ptr(cam), float(tan_fovx),
                                               float(tan_fovy), flags, rt.ptr(geom), rt.ptr(img),
-                                              rt.ptr(radii), None if use_async else C.addressof(n_host),
-                                              rt.ptr(max_rendered if max_rendered is not None else _max_rendered(dev))
-                                              if use_async else None))
+                                              rt.ptr(radii), None if use_async else C.addressof(n_host), mr_))
         # the scan of a capacity-mode pass (scatter kernel) leaves the per-tile instance counters of `img` at zero; a blocking
         # pass leaves its counts there (hgs_runtime.strand_step.ViewTable.counts_clean follows this)
         if P > 0:

@@ -3,14 +3,15 @@ gaussians, background)["render"]` per view under no_grad; SURVEY.md 3b, the unit
 whole forward of a view as ONE captured HIP graph:
 
     view select + clearing of the image buffer's counters   (riders of the next launch: hgs_runtime.strand_step.ViewTable)
-    parameters -> Gaussians                                  (hgs_hair_params_forward / hgs_cloud_params_forward)
-    preprocess, binning, sort, blend                         (hgs_forward_preprocess + hgs_forward_render, capacity mode)
+    parameters -> Gaussians -> preprocess                    (hgs_params_forward_preprocess; eager, blocking mode: hgs_params_forward
+                                                              + hgs_forward_preprocess; a cloud: the model's getters + the latter)
+    binning, sort, blend                                     (hgs_forward_render, capacity mode)
 
 A view switch re-points the graph's first node (no launch, no copies); the image is the one render() returns, bit for bit
 (tests/test_gpu_train.py::test_frame_renderer_equals_render).  render() itself stays the drop-in: ~20 host-side tensor
 operations per call keep it at about twice the kernels' time; this is the path for callers that render many views of a model
 that does not change in between (a viewer, render.py's loop, the evaluation of a checkpoint)."""
-import ctypes as C
+import functools
 
 import torch
 
@@ -70,12 +71,8 @@ class FrameRenderer:
                 # the kernel's sigmoid, 1 / (1 + expf(-x)), gives torch.sigmoid's bits (tests/test_gpu_frames.py pins that on
                 # 10^6 values): the opacity comes out of the same launch instead of one of its own
                 opacity = torch.empty((P, 1), **f32)
-
-                def fill(fused):     # (see hgs_runtime.strand_step._StrandIteration: same protocol)
-                    if fused and not vt.counts_clean:
-                        vt.flush_prologue()
-                    vt.fill_prologue(fu, behind_counts=fused)
-                hair = raster.HairSource(g._endpoints, pairs, g._width, g.dist_to_scale_factor, g._opacity, g._mask, fu, fill)
+                hair = raster.HairSource(g._endpoints, pairs, g._width, g.dist_to_scale_factor, g._opacity, g._mask, fu,
+                                         functools.partial(vt.carry_prologue, fu))
             else:
                 vt.flush_prologue()
                 xyz, scale, quat, opacity, hair = g.get_xyz, g.get_scaling, g.get_rotation, g.get_opacity, None

@@ -61,13 +61,10 @@ SIGNATURES = {
     "hgs_graph_set_prologue": (ci, [vp, vp, vp, ci, vp, cf, vp, vp, sz]),
     "hgs_set_view_queue": (ci, [vp, vp, ci, vp, cf, vp]),
     "hgs_select_view_queued": (ci, [vp, vp, ci, vp, vp, vp, vp]),
-    "hgs_hair_params_forward": (ci, [vp, ci, vp, vp, vp, cf, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "hgs_param_forward_bytes": (sz, []),
+    "hgs_params_forward": (ci, [vp, ci, vp, vp]),
+    "hgs_params_forward_preprocess": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp, vp]),
     "hgs_hair_params_backward": (ci, [vp, ci, ci, vp, vp, vp, cf, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]),
-    "hgs_cloud_params_forward": (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "hgs_cloud_forward_preprocess": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                          cf, cf, ci, vp, vp, vp, vp, vp]),
-    "hgs_hair_forward_preprocess": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp, cf, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                         cf, cf, ci, vp, vp, vp, vp, vp]),
     "hgs_cloud_params_backward": (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "hgs_loss_head_scratch_floats": (sz, [vp]),
     "hgs_loss_head_tail": (ci, [vp, vp, vp, vp]),
@@ -179,6 +176,13 @@ class StrandFusion(C.Structure):
                 ("n_endpoints", ci), ("head_tail", HeadTail), ("prologue", Prologue)]
 
 
+class ParamForward(C.Structure):
+    """include/hgs.h HgsParamForward."""
+    _fields_ = [("kind", ci), ("endpoints", vp), ("endpoint_pairs", vp), ("width", vp), ("dist_to_scale_factor", cf),
+                ("scaling_raw", vp), ("rotation_raw", vp), ("opacity_raw", vp), ("mask_raw", vp), ("means3D", vp), ("scale", vp),
+                ("quat", vp), ("opacity", vp), ("extra4", vp)]
+
+
 class ParamBackward(C.Structure):
     """include/hgs.h HgsParamBackward."""
     _fields_ = [("kind", ci), ("endpoints", vp), ("endpoint_pairs", vp), ("dist_to_scale_factor", cf), ("seg_contrib", vp),
@@ -194,7 +198,7 @@ HEAD_OUT = ["total", "l1", "dssim", "mask", "orientation", "smooth", "ori_count"
             "g_ori", "g_smooth", "total_fwd"]
 HEAD_NOUT = 16
 FUSED_PREPROCESS_MAX_TILES = 8192   # include/hgs.h HGS_FUSED_PREPROCESS_MAX_TILES
-ABI_VERSION = 10   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
+ABI_VERSION = 11   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
 
 
 def build(verbose=False):
@@ -225,7 +229,8 @@ def lib():
             raise HgsError(f"{LIB_PATH}: ABI version {L.hgs_abi_version()}, this binding needs {ABI_VERSION}: "
                            "rebuild with hgs_runtime.build()")
         for fn, st in (("hgs_view_targets_bytes", ViewTargets), ("hgs_head_params_bytes", HeadParams),
-                       ("hgs_strand_fusion_bytes", StrandFusion), ("hgs_param_backward_bytes", ParamBackward),
+                       ("hgs_strand_fusion_bytes", StrandFusion), ("hgs_param_forward_bytes", ParamForward),
+                       ("hgs_param_backward_bytes", ParamBackward),
                        ("hgs_adam_prep_bytes", AdamPrep), ("hgs_adam_inline_bytes", AdamInline),
                        ("hgs_raster_model_bytes", RasterModel)):
             if getattr(L, fn)() != C.sizeof(st):

@@ -1,5 +1,5 @@
 """The strand-Gaussian training iteration as ONE autograd node over the C ABI (include/hgs.h: hgs_select_view,
-hgs_hair_params_*, hgs_forward_render / hgs_backward with 7 channels, hgs_loss_head_*, hgs_densify_stats).
+hgs_params_forward*, hgs_forward_render / hgs_backward with 7 channels, hgs_loss_head_*, hgs_densify_stats).
 
 What the reference does between `gaussians` and `loss.backward()` in train.py:135-171 for a HairGaussianModel --
 getters (scene/hair_gaussian_model.py:134-201), three render() calls, loss_function (loss/losses.py:319-355) and the
@@ -11,6 +11,7 @@ approximated; tests/test_gpu_train.py checks loss, gradients and statistics agai
 Views live in a device-resident table (ViewTable); the iteration reads the current view through a 184-byte slot, so a
 captured HIP graph switches views with one tiny launch (hgs_select_view) and no image copies."""
 import ctypes as C
+import functools
 import os
 import math
 
@@ -154,7 +155,7 @@ class ViewTable:
 
     def fill_prologue(self, fu, behind_counts=False):
         """Hand a prologue(ride=True) to the StrandFusion of the parameter forward launch (once).  behind_counts: the launch
-        is hgs_hair_forward_preprocess, whose rider must leave the per-tile instance counters alone (include/hgs.h)."""
+        is hgs_params_forward_preprocess, whose rider must leave the per-tile instance counters alone (include/hgs.h)."""
         if self._rider is None:
             return
         view, lr, lr_dst = self._rider
@@ -165,6 +166,15 @@ class ViewTable:
         pro = fu.prologue
         pro.table, pro.view, pro.slot, pro.lr, pro.lr_dst = self.table.data_ptr(), view, self.slot.data_ptr(), lr, lr_dst
         pro.zero_ptr, pro.zero_bytes, pro.adam_prep = zp, zb, adam_prep
+
+    def carry_prologue(self, fu, fused):
+        """The `fill` of a diff_gaussian_rasterization._C parameter source whose first launch carries this table's prologue in
+        `fu`.  fused: that launch is parameters -> Gaussians -> preprocess in one; the riders then run beside the preprocess
+        workgroups, so the prologue must leave the tile counters alone -- which it may only if they are known to be zero
+        (counts_clean); otherwise it is launched on its own, clearing them."""
+        if fused and not self.counts_clean:
+            self.flush_prologue()
+        self.fill_prologue(fu, behind_counts=fused)
 
     def flush_prologue(self):
         """A prologue(ride=True) nobody carried: launch it now (callers whose first launch cannot take a rider)."""
@@ -368,10 +378,10 @@ def _params_stats(step, pb):
         step.last["stats_done"] = True
 
 
-def _tail_group(ctx, step, fu, scratch, out):
-    """The loss head's deferred tail, run by a spare workgroup of the backward's parameter launch."""
+def _tail_group(ctx, step, head_tail, scratch, out):
+    """The loss head's deferred tail, run by a spare workgroup of the backward's parameter launch: fills its HeadTail."""
     if ctx.defer_tail:
-        rt.check(rt.lib().hgs_loss_head_tail(C.byref(step.head), rt.ptr(scratch), rt.ptr(out), C.byref(fu.head_tail)))
+        rt.check(rt.lib().hgs_loss_head_tail(C.byref(step.head), rt.ptr(scratch), rt.ptr(out), C.byref(head_tail)))
 
 
 def _stats_group(step, fu, radii, g_means2D):
@@ -384,11 +394,57 @@ def _stats_group(step, fu, radii, g_means2D):
         step.last["stats_done"] = True
 
 
+def _decide_inline_adam(ctx, step, possible, why_not):
+    """Start of an iteration's forward.  ONE decision for the whole iteration: when the prologue carries the optimizer's plan (it
+    advances the step counters on the device), the backward MUST apply the update in its lanes -- or Adam's launch would advance
+    them a second time."""
+    step.refresh_inline_plan()
+    ctx.use_inline = step.inline_plan() is not None
+    if ctx.use_inline:
+        step.inline_adam._inline_done = False
+        if not possible:
+            raise rt.HgsError(f"in-lane Adam is enabled but this iteration's backward cannot apply it ({why_not}); disable it "
+                              "with enable_inline_adam(False)")
+
+
+def _require_no_inline_adam(ctx):
+    if ctx.use_inline:
+        raise rt.HgsError("the forward's prologue advanced Adam's step counters for an in-lane update this backward cannot apply")
+
+
+def _finish_forward(ctx, step, R, f_rest, d_extra, planes, radii, out, *saved):
+    """The end of an iteration's forward: what the backward needs, step.last, and the (loss, terms) pair."""
+    ctx.d_extra = d_extra
+    ctx.defer_tail = bool(step.head.defer_tail)
+    ctx.step, ctx.R, ctx.f_rest_k = step, R, f_rest.shape[1]
+    ctx.set_materialize_grads(False)   # no zero tensor for the (non-differentiable) terms output
+    ctx.save_for_backward(*saved)
+    step.last = {"planes": planes, "radii": radii, "terms": out}
+    terms = out.detach()
+    ctx.mark_non_differentiable(terms)
+    return out[0], terms
+
+
+def _smooth_group(step, fu, out=None, go=None):
+    """The smoothness term rides in extra workgroups of the parameter kernels (HgsStrandFusion): its group of `fu`; the backward
+    launches also take the head's outputs and the upstream gradient."""
+    idx, hp = step.smooth_pairs, step.head
+    fu.smooth_pairs, fu.n_smooth = idx.data_ptr(), int(idx.shape[0])
+    fu.cos_threshold, fu.eps = hp.cos_threshold, hp.eps
+    if out is not None:
+        fu.head_out, fu.grad_out = out.data_ptr(), go.data_ptr()
+
+
+def _split_sh(ctx, g_sh):
+    """dL/dSH [P,M,3] as the gradients of (f_dc, f_rest)."""
+    return (g_sh, None) if ctx.f_rest_k == 0 else (g_sh[:, :1], g_sh[:, 1:])
+
+
 class _StrandIteration(torch.autograd.Function):
     @staticmethod
     def forward(ctx, endpoints, width, opacity_raw, mask_raw, f_dc, f_rest, step):
         from diff_gaussian_rasterization import _C as raster
-        g, vt, L = step.gaussians, step.views, rt.lib()
+        g, vt = step.gaussians, step.views
         endpoints = rt.require_gpu_tensor(endpoints, "endpoints", torch.float32)
         width = rt.require_gpu_tensor(width, "width", torch.float32)
         opacity_raw = rt.require_gpu_tensor(opacity_raw, "opacity", torch.float32)
@@ -398,27 +454,16 @@ class _StrandIteration(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         xyz, scale, quat = torch.empty((P, 3), **f32), torch.empty((P, 3), **f32), torch.empty((P, 4), **f32)
         opacity, extra4 = torch.empty((P, 1), **f32), torch.empty((P, 4), **f32)
-        factor = float(g.dist_to_scale_factor)
-        stream = rt.current_stream()
-        step.refresh_inline_plan()
-        # ONE decision for the whole iteration: when the prologue carries the optimizer's plan (it advances the step counters on
-        # the device), the backward MUST apply the update in its lanes -- or Adam's launch would advance them a second time
-        ctx.use_inline = step.inline_plan() is not None
-        if ctx.use_inline:
-            step.inline_adam._inline_done = False
-            if not (step.fuse_param_backward and P > 0 and step.ep_segments is not None and step.ep_segments.shape[0] == E):
-                raise rt.HgsError("in-lane Adam is enabled but this iteration's backward cannot apply it (no segments, the fused "
-                                  "parameter backward off, or an endpoint adjacency that predates a topology change: call "
-                                  "refresh()); disable it with enable_inline_adam(False)")
+        _decide_inline_adam(ctx, step, step.fuse_param_backward and P > 0 and step.ep_segments is not None
+                            and step.ep_segments.shape[0] == E,
+                            "no segments, the fused parameter backward off, or an endpoint adjacency that predates a topology "
+                            "change: call refresh()")
         idx = step.smooth_pairs
-        hp = step.head
-        # the smoothness term rides in extra workgroups of the parameter kernels (HgsStrandFusion)
         fu = rt.StrandFusion()
         smooth_partials = pair_grads = None
-        if idx is not None and hp.lambda_smooth > 0:
+        if idx is not None and step.head.lambda_smooth > 0:
             smooth_partials = torch.empty((2 * ((idx.shape[0] + 255) // 256),), **f32)
-            fu.smooth_pairs, fu.n_smooth = idx.data_ptr(), int(idx.shape[0])
-            fu.cos_threshold, fu.eps = hp.cos_threshold, hp.eps
+            _smooth_group(step, fu)
             fu.smooth_partials = smooth_partials.data_ptr()
             # the pairs' unit gradients for the backward's endpoint gather (they do not depend on the rasterizer: the forward's
             # spare workgroups compute them beside the preprocess workgroups, HgsStrandFusion.smooth_pair_grads)
@@ -426,42 +471,22 @@ class _StrandIteration(torch.autograd.Function):
                 pair_grads = torch.empty((idx.shape[0], 2, 4), **f32)
                 fu.smooth_pair_grads = pair_grads.data_ptr()
         shs = f_dc if f_rest.numel() == 0 else torch.cat((f_dc, f_rest), dim=1)
-        if step.fuse_preprocess:
-            # parameters -> Gaussians -> preprocess as ONE launch where the pass runs in capacity mode (HairSource); the riders
-            # then run beside the preprocess workgroups, so the prologue must leave the tile counters alone -- which it may
-            # only if they are known to be zero (ViewTable.counts_clean); otherwise it is launched on its own, clearing them
-            def fill(fused):
-                if fused and not vt.counts_clean:
-                    vt.flush_prologue()
-                vt.fill_prologue(fu, behind_counts=fused)
-            hair = raster.HairSource(endpoints, pairs, width, factor, opacity_raw, mask_raw, fu, fill)
-        else:
-            hair = None
-            vt.fill_prologue(fu)
-            with torch.cuda.device(dev):
-                rt.check(L.hgs_hair_params_forward(stream, P, rt.ptr(endpoints), rt.ptr(pairs), rt.ptr(width), factor,
-                                                   rt.ptr(opacity_raw), rt.ptr(mask_raw), rt.ptr(xyz), rt.ptr(scale),
-                                                   rt.ptr(quat), None, rt.ptr(opacity), rt.ptr(extra4), C.byref(fu)))
+        # parameters -> Gaussians -> preprocess as ONE launch where the pass runs in capacity mode, else (or with fuse_preprocess
+        # off) as two; either way the first of them carries the prologue (ViewTable.carry_prologue)
+        hair = raster.HairSource(endpoints, pairs, width, g.dist_to_scale_factor, opacity_raw, mask_raw, fu,
+                                 functools.partial(vt.carry_prologue, fu), fuse=step.fuse_preprocess)
         R, planes, radii, geom, binning, img, scratch, out, d_extra = _raster_head_forward(
             step, xyz, scale, quat, opacity, extra4, shs, endpoints, idx, smooth_partials, E, hair=hair)
-        ctx.d_extra = d_extra
-        ctx.defer_tail = bool(step.head.defer_tail)
         ctx.fused_smooth = smooth_partials is not None
-        ctx.step, ctx.R, ctx.f_rest_k = step, R, f_rest.shape[1]
-        ctx.set_materialize_grads(False)   # no zero tensor for the (non-differentiable) terms output
-        ctx.save_for_backward(endpoints, width, pairs, xyz, scale, quat, opacity, extra4, shs, planes, radii, geom, binning,
-                              img, scratch, out)
         ctx.pair_grads = pair_grads
-        step.last = {"planes": planes, "radii": radii, "terms": out}
-        terms = out.detach()
-        ctx.mark_non_differentiable(terms)
-        return out[0], terms
+        return _finish_forward(ctx, step, R, f_rest, d_extra, planes, radii, out, endpoints, width, pairs, xyz, scale, quat,
+                               opacity, extra4, shs, planes, radii, geom, binning, img, scratch, out)
 
     @staticmethod
     def backward(ctx, go, _):
         from diff_gaussian_rasterization import _C as raster
         step, L = ctx.step, rt.lib()
-        g, vt, hp = step.gaussians, step.views, step.head
+        g = step.gaussians
         (endpoints, width, pairs, xyz, scale, quat, opacity, extra4, shs, planes, radii, geom, binning, img, scratch,
          out) = ctx.saved_tensors
         dev, P, E = endpoints.device, pairs.shape[0], endpoints.shape[0]
@@ -489,13 +514,10 @@ class _StrandIteration(torch.autograd.Function):
                 params=pb)
             fu = rt.StrandFusion()
             if ctx.fused_smooth:
-                idx = step.smooth_pairs
-                fu.smooth_pairs, fu.n_smooth = idx.data_ptr(), int(idx.shape[0])
-                fu.cos_threshold, fu.eps = hp.cos_threshold, hp.eps
-                fu.head_out, fu.grad_out = out.data_ptr(), go.data_ptr()
+                _smooth_group(step, fu, out, go)
                 if ctx.pair_grads is not None:
                     fu.smooth_pair_grads = ctx.pair_grads.data_ptr()
-            _tail_group(ctx, step, fu, scratch, out)
+            _tail_group(ctx, step, fu.head_tail, scratch, out)
             fu.ep_segments, fu.n_endpoints = step.ep_segments.data_ptr(), E
             fu.ep_pairs = None if step.ep_pairs is None else step.ep_pairs.data_ptr()
             with torch.cuda.device(dev):
@@ -504,25 +526,17 @@ class _StrandIteration(torch.autograd.Function):
             if plan is not None:
                 plan.applied()
             step.last["dmean2D"] = g_means2D
-            if ctx.f_rest_k == 0:
-                d_dc, d_rest = g_sh, None
-            else:
-                d_dc, d_rest = g_sh[:, :1], g_sh[:, 1:]
-            return d_ep, d_w, d_o, d_m, d_dc, d_rest, None
-        if ctx.use_inline:
-            raise rt.HgsError("the forward's prologue advanced Adam's step counters for an in-lane update this backward cannot apply")
+            return (d_ep, d_w, d_o, d_m, *_split_sh(ctx, g_sh), None)
+        _require_no_inline_adam(ctx)
         go, (g_means2D, g_ex, g_opac, g_means3D, g_sh, g_scales, g_rot) = _head_raster_backward(
             ctx, step, go, xyz, scale, quat, shs, planes, radii, geom, binning, img, scratch, out, endpoints,
             None if gather else d_ep, E)
         stream = rt.current_stream()
         fu = rt.StrandFusion()
         if ctx.fused_smooth:      # smoothness gradient: extra workgroups of the same launch, same d_ep
-            idx = step.smooth_pairs
-            fu.smooth_pairs, fu.n_smooth = idx.data_ptr(), int(idx.shape[0])
-            fu.cos_threshold, fu.eps = hp.cos_threshold, hp.eps
-            fu.head_out, fu.grad_out = out.data_ptr(), go.data_ptr()
+            _smooth_group(step, fu, out, go)
         _stats_group(step, fu, radii, g_means2D)
-        _tail_group(ctx, step, fu, scratch, out)
+        _tail_group(ctx, step, fu.head_tail, scratch, out)
         if gather:
             fu.ep_segments, fu.n_endpoints = step.ep_segments.data_ptr(), E
             fu.ep_pairs = None if step.ep_pairs is None else step.ep_pairs.data_ptr()
@@ -533,11 +547,7 @@ class _StrandIteration(torch.autograd.Function):
                                                 rt.ptr(g_ex), 1, rt.ptr(d_ep), rt.ptr(d_w), rt.ptr(d_o), rt.ptr(d_m),
                                                 C.byref(fu)))
         step.last["dmean2D"] = g_means2D      # RGB-only screen-space gradient: what the densification statistics see
-        if ctx.f_rest_k == 0:
-            d_dc, d_rest = g_sh, None
-        else:
-            d_dc, d_rest = g_sh[:, :1], g_sh[:, 1:]
-        return d_ep, d_w, d_o, d_m, d_dc, d_rest, None
+        return (d_ep, d_w, d_o, d_m, *_split_sh(ctx, g_sh), None)
 
 
 class FusedStrandStep:
@@ -561,7 +571,7 @@ class FusedStrandStep:
         self.skip_unread_blocks = bool(getattr(opt, "skip_unread_blocks", True))
         self._tile_maxc_offset = None
         self.poison_unwritten = False   # tests: dL/dimage starts as NaN
-        # strand parameters -> Gaussians -> preprocess as one launch (hgs_hair_forward_preprocess) where the pass allows it
+        # raw parameters -> Gaussians -> preprocess as one launch (hgs_params_forward_preprocess) where the pass allows it
         self.fuse_preprocess = bool(getattr(opt, "fuse_preprocess", True)) and os.environ.get("HGS_FUSE_PREPROCESS", "1") != "0"
         # the backward mirror: parameters' backward in the rasterizer backward's per-Gaussian lanes (hgs_backward_multi_params)
         self.fuse_param_backward = bool(getattr(opt, "fuse_param_backward", True)) and os.environ.get("HGS_FUSE_PARAM_BACKWARD", "1") != "0"
@@ -653,11 +663,10 @@ class FusedStrandStep:
 
 class _CloudIteration(torch.autograd.Function):
     """The same iteration for the Stage-I Gaussian cloud (scene/gaussian_model.py): raw (scaling, rotation, opacity, mask)
-    -> rasterizer inputs by hgs_cloud_params_*; xyz and the SH features go to the rasterizer as they are."""
+    -> rasterizer inputs by hgs_params_forward* / hgs_cloud_params_backward; xyz and the SH features go to the rasterizer as they are."""
 
     @staticmethod
     def forward(ctx, xyz, scaling_raw, rotation_raw, opacity_raw, mask_raw, f_dc, f_rest, step):
-        L = rt.lib()
         xyz = rt.require_gpu_tensor(xyz, "xyz", torch.float32)
         scaling_raw = rt.require_gpu_tensor(scaling_raw, "scaling", torch.float32)
         rotation_raw = rt.require_gpu_tensor(rotation_raw, "rotation", torch.float32)
@@ -669,40 +678,16 @@ class _CloudIteration(torch.autograd.Function):
         opacity, extra4 = torch.empty((P, 1), **f32), torch.empty((P, 4), **f32)
         from diff_gaussian_rasterization import _C as raster
         fu = rt.StrandFusion()
-        vt = step.views
-        step.refresh_inline_plan()
-        ctx.use_inline = step.inline_plan() is not None      # (one decision per iteration: see _StrandIteration.forward)
-        if ctx.use_inline:
-            step.inline_adam._inline_done = False
-            if not (step.fuse_param_backward and P > 0):
-                raise rt.HgsError("in-lane Adam is enabled but this iteration's backward cannot apply it (no Gaussians, or the "
-                                  "fused parameter backward off); disable it with enable_inline_adam(False)")
-        if step.fuse_preprocess:      # (as _StrandIteration: parameters -> Gaussians -> preprocess as one launch)
-            def fill(fused):
-                if fused and not vt.counts_clean:
-                    vt.flush_prologue()
-                vt.fill_prologue(fu, behind_counts=fused)
-            src = raster.CloudSource(scaling_raw, rotation_raw, opacity_raw, mask_raw, fu, fill)
-        else:
-            src = None
-            vt.fill_prologue(fu)
-            with torch.cuda.device(dev):
-                rt.check(L.hgs_cloud_params_forward(rt.current_stream(), P, rt.ptr(scaling_raw), rt.ptr(rotation_raw),
-                                                    rt.ptr(opacity_raw), rt.ptr(mask_raw), rt.ptr(scale), rt.ptr(quat),
-                                                    rt.ptr(opacity), rt.ptr(extra4), C.byref(fu)))
+        _decide_inline_adam(ctx, step, step.fuse_param_backward and P > 0, "no Gaussians, or the fused parameter backward off")
+        # (as _StrandIteration: the pass's first launch derives the Gaussians and carries the prologue)
+        src = raster.CloudSource(scaling_raw, rotation_raw, opacity_raw, mask_raw, fu,
+                                 functools.partial(step.views.carry_prologue, fu), fuse=step.fuse_preprocess)
         shs = f_dc if f_rest.numel() == 0 else torch.cat((f_dc, f_rest), dim=1)
         R, planes, radii, geom, binning, img, scratch, out, d_extra = _raster_head_forward(
             step, xyz, scale, quat, opacity, extra4, shs, None, None, None, 0, hair=src)
-        ctx.d_extra, ctx.fused_smooth = d_extra, True   # (no smoothness term for a cloud: nothing to launch)
-        ctx.defer_tail = bool(step.head.defer_tail)
-        ctx.step, ctx.R, ctx.f_rest_k = step, R, f_rest.shape[1]
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(xyz, scaling_raw, rotation_raw, scale, quat, opacity, extra4, shs, planes, radii, geom, binning,
-                              img, scratch, out)
-        step.last = {"planes": planes, "radii": radii, "terms": out}
-        terms = out.detach()
-        ctx.mark_non_differentiable(terms)
-        return out[0], terms
+        ctx.fused_smooth = True   # (no smoothness term for a cloud: nothing to launch)
+        return _finish_forward(ctx, step, R, f_rest, d_extra, planes, radii, out, xyz, scaling_raw, rotation_raw, scale, quat,
+                               opacity, extra4, shs, planes, radii, geom, binning, img, scratch, out)
 
     @staticmethod
     def backward(ctx, go, _):
@@ -725,36 +710,26 @@ class _CloudIteration(torch.autograd.Function):
             if plan is not None:      # Adam in the backward's own lanes (include/hgs.h HgsAdamSlot)
                 gm = step.gaussians
                 plan.fill(pb.adam, (gm._xyz, gm._scaling, gm._rotation, gm._opacity, gm._mask, gm._features_dc))
-            if ctx.defer_tail:
-                rt.check(L.hgs_loss_head_tail(C.byref(step.head), rt.ptr(scratch), rt.ptr(out), C.byref(pb.head_tail)))
+            _tail_group(ctx, step, pb.head_tail, scratch, out)
             go, (g_means2D, _, _, _, g_sh, _, _) = _head_raster_backward(
                 ctx, step, go, xyz, scale, quat, shs, planes, radii, geom, binning, img, scratch, out, None, None, 0, params=pb)
             if plan is not None:
                 plan.applied()
             step.last["dmean2D"] = g_means2D
-            if ctx.f_rest_k == 0:
-                d_dc, d_rest = g_sh, None
-            else:
-                d_dc, d_rest = g_sh[:, :1], g_sh[:, 1:]
-            return g_means3D, d_s, d_r, d_o, d_m, d_dc, d_rest, None
-        if ctx.use_inline:
-            raise rt.HgsError("the forward's prologue advanced Adam's step counters for an in-lane update this backward cannot apply")
+            return (g_means3D, d_s, d_r, d_o, d_m, *_split_sh(ctx, g_sh), None)
+        _require_no_inline_adam(ctx)
         go, (g_means2D, g_ex, g_opac, g_means3D, g_sh, g_scales, g_rot) = _head_raster_backward(
             ctx, step, go, xyz, scale, quat, shs, planes, radii, geom, binning, img, scratch, out, None, None, 0)
         fu = rt.StrandFusion()
         _stats_group(step, fu, radii, g_means2D)
-        _tail_group(ctx, step, fu, scratch, out)
+        _tail_group(ctx, step, fu.head_tail, scratch, out)
         with torch.cuda.device(dev):
             rt.check(L.hgs_cloud_params_backward(rt.current_stream(), P, rt.ptr(scaling_raw), rt.ptr(rotation_raw),
                                                  rt.ptr(opacity), rt.ptr(extra4), rt.ptr(g_scales), rt.ptr(g_rot),
                                                  rt.ptr(g_opac), rt.ptr(g_ex), rt.ptr(d_s), rt.ptr(d_r), rt.ptr(d_o),
                                                  rt.ptr(d_m), C.byref(fu)))
         step.last["dmean2D"] = g_means2D
-        if ctx.f_rest_k == 0:
-            d_dc, d_rest = g_sh, None
-        else:
-            d_dc, d_rest = g_sh[:, :1], g_sh[:, 1:]
-        return g_means3D, d_s, d_r, d_o, d_m, d_dc, d_rest, None
+        return (g_means3D, d_s, d_r, d_o, d_m, *_split_sh(ctx, g_sh), None)
 
 
 class FusedCloudStep(FusedStrandStep):

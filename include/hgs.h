@@ -50,7 +50,7 @@ extern "C" {
  * 9: tile culling, the record form and the row sums are flag bits of each call instead of process-wide setters, and one render,
  * backward and size function each serves 3 and 7 channels; 10: hgs_pointcloud_normals / hgs_pointcloud_normals_scratch_bytes);
  * the Python binding refuses a library whose version or struct sizes differ from its own */
-#define HGS_ABI_VERSION 10
+#define HGS_ABI_VERSION 11
 #define HGS_TILE 16 /* cuda_rasterizer/config.h:16-17 */
 
 int hgs_abi_version(void);
@@ -275,7 +275,7 @@ int hgs_select_view(void* stream, const HgsViewTargets* table, int view, HgsView
 int hgs_iteration_prologue(void* stream, const HgsViewTargets* table, int view, HgsViewTargets* slot, float lr, float* lr_dst,
                            void* zero_ptr, size_t zero_bytes, const HgsAdamPrep* adam_prep /* NULL: none */);
 int hgs_image_zero_range(int W, int H, size_t* offset, size_t* bytes);   /* of an image_buf of hgs_image_bytes(W, H) */
-/* The same prologue as a rider of another launch: hgs_hair_params_forward / hgs_cloud_params_forward -- the first launch of
+/* The same prologue as a rider of another launch: hgs_params_forward -- the first launch of
  * an iteration, which needs neither the view nor the counters -- run it in spare workgroups when HgsStrandFusion.prologue
  * is filled in (table != NULL): no launch of its own in front of the iteration (4 us of a 290 us iteration).  The graph
  * functions below find and re-point such a rider exactly like a stand-alone prologue launch. */
@@ -324,7 +324,7 @@ typedef struct HgsHeadTail {
   int bce, ori, smooth;
 } HgsHeadTail;
 
-/* hgs_hair_params_forward/backward: hgs_strand_geometry_* plus the appearance activations of the same Gaussians
+/* hgs_params_forward (HGS_PARAMS_HAIR) / hgs_hair_params_backward: hgs_strand_geometry_* plus the appearance activations of the same Gaussians
  *   (scene/gaussian_model.py:93-99 get_opacity / get_mask = sigmoid) and the 4 extra blended channels of the
  *   single-pass rasterizer, extra4 = [sigmoid(mask_raw), dir.xyz].  backward: g_extra4 [P,4] carries the gradient of
  *   the mask channel and of the direction (added to g_dir); `opacity`/`extra4` are the forward outputs;
@@ -351,16 +351,29 @@ typedef struct HgsStrandFusion {
   HgsHeadTail head_tail;   /* backward: out != NULL -> one spare workgroup of the launch runs the loss head's deferred tail */
   HgsPrologue prologue;    /* forward: table != NULL -> spare workgroups of the launch run the iteration prologue */
 } HgsStrandFusion;
-int hgs_hair_params_forward(void* stream, int P, const float* endpoints, const long long* endpoint_pairs,
-                            const float* width, float dist_to_scale_factor, const float* opacity_raw,
-                            const float* mask_raw, float* xyz, float* scale, float* quat, float* dir, float* opacity,
-                            float* extra4, const HgsStrandFusion* fusion);
-/* hgs_hair_forward_preprocess: hgs_hair_params_forward AND hgs_forward_preprocess of the same strand model as ONE launch
- *   (the iteration's first: every lane derives its segment's Gaussian -- written to xyz / scale / quat / opacity / extra4 for
- *   the backward and the render entry points, bit-identical to hgs_hair_params_forward's -- and preprocesses it from
+/* The model's raw parameters behind the Gaussians of a pass, for the launches that derive them -- the forward counterpart of
+ * HgsParamBackward (below), with the same `kind`. */
+enum { HGS_PARAMS_HAIR = 1, HGS_PARAMS_CLOUD = 2 };
+typedef struct HgsParamForward {
+  int kind;                                                                /* HGS_PARAMS_HAIR | HGS_PARAMS_CLOUD */
+  const float* endpoints; const long long* endpoint_pairs; const float* width; float dist_to_scale_factor;   /* hair: in */
+  const float* scaling_raw; const float* rotation_raw;                     /* cloud: in ([P,4] rotation: 16-byte aligned for the one-launch form) */
+  const float* opacity_raw; const float* mask_raw;                         /* in [P] */
+  /* the derived Gaussians: means3D [P,3] hair: out, cloud: the model's own parameter, in;  scale [P,3], quat [P,4], opacity [P],
+   * extra4 [P,4]: out (quat / extra4: 16-byte aligned for the one-launch form) */
+  float* means3D; float* scale; float* quat; float* opacity; float* extra4;
+} HgsParamForward;
+size_t hgs_param_forward_bytes(void);    /* sizeof(HgsParamForward) */
+/* parameters -> Gaussians in one launch (strand_fwd_kernel / cloud_fwd_kernel by `kind`; the cloud form is described at
+ *   hgs_cloud_params_backward and uses only the prologue group of `fusion`).  The segments' direction alone: hgs_strand_geometry_forward. */
+int hgs_params_forward(void* stream, int P, const HgsParamForward* params, const HgsStrandFusion* fusion);
+/* hgs_params_forward_preprocess: hgs_params_forward AND hgs_forward_preprocess of the same model as ONE launch
+ *   (the iteration's first: every lane derives its Gaussian -- written to means3D (hair) / scale / quat / opacity / extra4 for
+ *   the backward and the render entry points, bit-identical to hgs_params_forward's -- and preprocesses it from
  *   registers; SH colours only, scale_modifier 1).  Capacity mode only (max_rendered as in hgs_forward_preprocess; no
  *   blocking count), at most 8192 tiles.  `flags`: HGS_IMAGE_PREZEROED as in hgs_forward_preprocess.  The riders of
- *   `fusion` (smoothness partial sums, HgsPrologue) run BESIDE the preprocess workgroups, hence two rules:
+ *   `fusion` (smoothness partial sums, HgsPrologue; a cloud: the prologue group only) run BESIDE the preprocess workgroups, hence
+ *   two rules:
  *     - viewmatrix / projmatrix / campos are read from fusion->prologue.table[view] when a prologue rides (the slot is being
  *       written by that very launch; the three pointers are used only without a prologue);
  *     - the prologue's zero range must start BEHIND the per-tile instance counters (hgs_image_layout: from
@@ -368,21 +381,10 @@ int hgs_hair_params_forward(void* stream, int P, const float* endpoints, const l
  *       hgs_forward_render in capacity mode leaves behind (its scan clears what it has read); after a pass in blocking mode,
  *       or on a buffer of unknown content, run hgs_iteration_prologue with the full range of hgs_image_zero_range first. */
 #define HGS_FUSED_PREPROCESS_MAX_TILES 8192
-int hgs_hair_forward_preprocess(void* stream, int P, int D, int M, int W, int H, const float* endpoints,
-                                const long long* endpoint_pairs, const float* width, float dist_to_scale_factor,
-                                const float* opacity_raw, const float* mask_raw, const float* shs, float* xyz, float* scale,
-                                float* quat, float* opacity, float* extra4, const float* viewmatrix, const float* projmatrix,
-                                const float* campos, float tan_fovx, float tan_fovy, int flags, void* geom_buf,
-                                void* image_buf, int* radii, unsigned int* max_rendered, const HgsStrandFusion* fusion);
-/* The same for the Stage-I cloud: hgs_cloud_params_forward AND hgs_forward_preprocess as one launch (means3D is the model's
- *   own parameter; scale / quat / opacity / extra4 are written as hgs_cloud_params_forward writes them, bit for bit); only the
- *   prologue group of `fusion` is used. */
-int hgs_cloud_forward_preprocess(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* scaling_raw,
-                                 const float* rotation_raw, const float* opacity_raw, const float* mask_raw, const float* shs,
-                                 float* scale, float* quat, float* opacity, float* extra4, const float* viewmatrix,
-                                 const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, int flags,
-                                 void* geom_buf, void* image_buf, int* radii, unsigned int* max_rendered,
-                                 const HgsStrandFusion* fusion);
+int hgs_params_forward_preprocess(void* stream, int P, int D, int M, int W, int H, const HgsParamForward* params, const float* shs,
+                                  const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                                  float tan_fovy, int flags, void* geom_buf, void* image_buf, int* radii,
+                                  unsigned int* max_rendered, const HgsStrandFusion* fusion);
 int hgs_hair_params_backward(void* stream, int P, int E, const float* endpoints, const long long* endpoint_pairs,
                              const float* width, float dist_to_scale_factor, const float* opacity, const float* extra4,
                              const float* g_xyz, const float* g_scale, const float* g_quat, const float* g_dir,
@@ -390,7 +392,7 @@ int hgs_hair_params_backward(void* stream, int P, int E, const float* endpoints,
                              float* d_endpoints, float* d_width, float* d_opacity_raw, float* d_mask_raw,
                              const HgsStrandFusion* fusion);
 
-/* ---- hgs_backward_multi_params: the BACKWARD mirror of hgs_hair_forward_preprocess / hgs_cloud_forward_preprocess (round 5).
+/* ---- hgs_backward_multi_params: the BACKWARD mirror of hgs_params_forward_preprocess (round 5).
  *   hgs_backward (n_extra 4) whose last per-Gaussian launch also applies the backward of the derivation parameters -> Gaussian, in the
  *   lane that has just finished the Gaussian's gradients (they never travel through memory):
  *     HGS_PARAMS_HAIR   what hgs_hair_params_backward's per-segment lanes compute -- d_width, d_opacity_raw, d_mask_raw, the
@@ -405,7 +407,6 @@ int hgs_hair_params_backward(void* stream, int P, int E, const float* endpoints,
  *   flags: HGS_ROWS_* as in hgs_backward.
  *   `extra4` / `opacity`-like inputs are the FORWARD's outputs of the same pass.  Optional (NULL = skipped): dL_dmeans2D_rgb
  *   [P,3], the statistics group (max_radii2D / grad_accum / denom, all three or none). ---- */
-enum { HGS_PARAMS_HAIR = 1, HGS_PARAMS_CLOUD = 2 };
 typedef struct HgsParamBackward {
   int kind;                                                                /* HGS_PARAMS_HAIR | HGS_PARAMS_CLOUD */
   const float* endpoints; const long long* endpoint_pairs; float dist_to_scale_factor;   /* hair: in */
@@ -432,15 +433,12 @@ int hgs_backward_multi_params(void* stream, int P, int D, int M, int R, int W, i
 int hgs_hair_endpoint_gather(void* stream, int E, const float* seg_contrib, const float* endpoints, float* d_endpoints,
                              const HgsStrandFusion* fusion, const HgsAdamInline* adam);
 
-/* hgs_cloud_params_forward/backward: the Stage-I counterpart of hgs_hair_params_* -- the rasterizer-facing getters of the
+/* hgs_params_forward (HGS_PARAMS_CLOUD) / hgs_cloud_params_backward: the Stage-I counterpart of the strand forms -- the rasterizer-facing getters of the
  *   Gaussian cloud (scene/gaussian_model.py:118-157) and their autograd in one launch each:
  *   scale = exp(scaling_raw); quat = rotation_raw / max(|rotation_raw|, 1e-12) (F.normalize); opacity / mask = sigmoid;
  *   direction = column argmax(scale) of build_rotation(rotation_raw) (get_orientation: the longest axis in world space);
  *   extra4 = [mask, direction].  backward: g_scale / g_quat / g_opacity / g_extra4 are the rasterizer's gradients;
  *   `fusion` may carry the densification-statistics group of HgsStrandFusion (its smoothness group is ignored). */
-int hgs_cloud_params_forward(void* stream, int P, const float* scaling_raw, const float* rotation_raw,
-                             const float* opacity_raw, const float* mask_raw, float* scale, float* quat, float* opacity,
-                             float* extra4, const HgsStrandFusion* fusion /* NULL, or its prologue group */);
 int hgs_cloud_params_backward(void* stream, int P, const float* scaling_raw, const float* rotation_raw,
                               const float* opacity, const float* extra4, const float* g_scale, const float* g_quat,
                               const float* g_opacity, const float* g_extra4, float* d_scaling_raw, float* d_rotation_raw,

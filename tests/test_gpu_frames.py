@@ -128,7 +128,7 @@ def test_frame_renderer_batches():
 
 
 def test_kernel_sigmoid_has_torch_sigmoids_bits():
-    """FrameRenderer takes the strands' opacity from hgs_hair_params_forward (1 / (1 + expf(-x))) where render() calls
+    """FrameRenderer takes the strands' opacity from hgs_params_forward (1 / (1 + expf(-x))) where render() calls
     torch.sigmoid: the two agree bit for bit (10^6 values over the range of opacity logits, and the special cases)."""
     import ctypes as C
     import numpy as np
@@ -144,8 +144,10 @@ def test_kernel_sigmoid_has_torch_sigmoids_bits():
     f32 = dict(dtype=torch.float32, device="cuda")
     xyz, scale, quat = torch.empty((P, 3), **f32), torch.empty((P, 3), **f32), torch.empty((P, 4), **f32)
     o, e4 = torch.empty((P, 1), **f32), torch.empty((P, 4), **f32)
-    rt.check(rt.lib().hgs_hair_params_forward(rt.current_stream(), P, rt.ptr(ep), rt.ptr(pairs), rt.ptr(w), 1.0, rt.ptr(x), rt.ptr(x),
-                                              rt.ptr(xyz), rt.ptr(scale), rt.ptr(quat), None, rt.ptr(o), rt.ptr(e4), None))
+    pf = rt.ParamForward(kind=rt.PARAMS_HAIR, endpoints=rt.ptr(ep), endpoint_pairs=rt.ptr(pairs), width=rt.ptr(w),
+                         dist_to_scale_factor=1.0, opacity_raw=rt.ptr(x), mask_raw=rt.ptr(x), means3D=rt.ptr(xyz),
+                         scale=rt.ptr(scale), quat=rt.ptr(quat), opacity=rt.ptr(o), extra4=rt.ptr(e4))
+    rt.check(rt.lib().hgs_params_forward(rt.current_stream(), P, C.byref(pf), None))
     ref = torch.sigmoid(x)
     assert torch.equal(o.view(torch.int32), ref.view(torch.int32))
     assert torch.equal(e4[:, 0].contiguous().view(torch.int32), ref[:, 0].contiguous().view(torch.int32))

@@ -1194,8 +1194,8 @@ def test_loss_head_skips_all_zero_blocks_exactly(hw):
 
 
 def test_one_launch_parameters_and_preprocess_equals_two_launches():
-    """hgs_hair_forward_preprocess (strand parameters -> Gaussians -> preprocess in ONE kernel, the riders beside it) against
-    hgs_hair_params_forward + hgs_forward_preprocess: derived Gaussians, radii, the geometry buffer, the image and every
+    """hgs_params_forward_preprocess (strand parameters -> Gaussians -> preprocess in ONE kernel, the riders beside it) against
+    hgs_params_forward + hgs_forward_preprocess: derived Gaussians, radii, the geometry buffer, the image and every
     gradient bit for bit (the smoothness partial sums ride in a kernel of another translation unit: that term to 1e-6)."""
     from arguments import OptimizationParams
     from diff_gaussian_rasterization import _C as raster
@@ -1259,7 +1259,7 @@ def test_one_launch_parameters_and_preprocess_equals_two_launches():
 
 
 def test_one_launch_cloud_parameters_and_preprocess_equals_two_launches():
-    """hgs_cloud_forward_preprocess against hgs_cloud_params_forward + hgs_forward_preprocess (Stage-I cloud iteration): loss
+    """hgs_params_forward_preprocess against hgs_params_forward + hgs_forward_preprocess (Stage-I cloud iteration): loss
     terms, image, radii and every parameter gradient bit for bit."""
     from arguments import OptimizationParams
     from diff_gaussian_rasterization import _C as raster
