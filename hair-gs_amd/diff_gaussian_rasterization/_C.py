@@ -1,6 +1,7 @@
 """Drop-in for the reference's pybind11 module `diff_gaussian_rasterization._C`
 (submodules/diff-gaussian-rasterization/ext.cpp:15-19): same three functions, same argument order, same
 return tuples -- implemented over the C ABI of libhgs.so (include/hgs.h) with ctypes."""
+import contextlib
 import ctypes as C
 import os
 
@@ -8,21 +9,22 @@ import torch
 
 import hgs_runtime as rt
 
-# ---- optional asynchronous mode -----------------------------------------------------------------------------------
-# Default (async_mode False) = the reference's behaviour: every forward blocks once on `num_rendered`
-# (cuda_rasterizer/rasterizer_impl.cu:280-281) to size the binning buffer exactly.
-# With set_async(True) the forward never blocks: the binning buffer is sized from a CAPACITY (slack x the largest
-# instance count seen so far), the true count and the overflow flag of every pass are copied to pinned host memory
-# asynchronously, and the caller validates them ONCE per training step with check_async() (one synchronisation
-# instead of three).  If a pass needed more than its capacity, check_async() raises HgsCapacityOverflow after growing
-# the capacity: the caller discards the step's gradients and repeats it.  `num_rendered` returned by
-# rasterize_gaussians is then the capacity (it only sizes/carves buffers downstream).
+# ---- capacity mode: its bookkeeping lives in this module and nowhere else ---------------------------------------------
+# Default (blocking mode) = the reference's behaviour: every forward waits once for `num_rendered`
+# (cuda_rasterizer/rasterizer_impl.cu:280-281) to size the binning buffer exactly.  After set_async(True) only the first pass
+# does, and learns a CAPACITY from it (raise_capacity); later passes size the buffer from the capacity (their `num_rendered`)
+# and never wait: the library keeps a sticky maximum of the true counts in one int32 word per device (hgs_forward_preprocess
+# max_rendered).  A pass on this module's word sets the pending mark (`dirty`) and lowers `cap_used` to its capacity;
+# check_async() clears the marks and judges those passes, set_async() and discard_pending() clear them without a verdict.
+# A pass given the caller's own `max_rendered` word sets no mark: that caller reads its word (read_max_rendered) and judges.
 IMAGE_PREZEROED = 2   # include/hgs.h HGS_IMAGE_PREZEROED (flag in `prefiltered`)
 COUNT_ROW_RUNS = 4    # include/hgs.h HGS_COUNT_ROW_RUNS
 TILE_CULL = 8         # include/hgs.h HGS_TILE_CULL
 RECORDS_PACKED, RECORDS_LAZY = 16, 32   # include/hgs.h HGS_RECORDS_* (flags of hgs_forward_render)
 ROWS_INLINE, ROWS_REDUCE = 64, 128      # include/hgs.h HGS_ROWS_* (flags of hgs_backward)
-_state = {"last_R": 0, "last_counts_clean": False, "async": False, "cap": 0, "slack": 1.5, "dirty": False, "cap_used": None, "max_R": {}, "cull": None}
+_state = {"async": False, "slack": 1.5, "cap": 0, "dirty": False, "cap_used": None,   # (cap 0: none learnt yet; cap_used: the smallest a pending pass ran with)
+          "max_R": {}, "last_exact_R": 0, "last_counts_clean": False,                   # device -> sticky word; side results of the last pass / check
+          "cull": None, "row_reduce": None, "lazy_records": None, "row_runs": None}   # the tri-state mode setters
 
 
 class HgsCapacityOverflow(RuntimeError):
@@ -69,13 +71,13 @@ def set_row_reduce(mode):
     capacity rule otherwise.  train.GraphedStep.capture() sets it from the instance counts its warm-up passes measured, so that the form
     follows the MODEL (and with it every replay and every eager iteration until the next capture), not the capacity a run
     happens to hold: a run that rolls back and raises its capacity keeps the arithmetic of one that never overflowed."""
-    was = _state.get("row_reduce")
+    was = _state["row_reduce"]
     _state["row_reduce"] = None if mode is None else bool(mode)
     return was
 
 
 def _row_reduce_flags(P, R):
-    mode = _pinned(_state.get("row_reduce"), "HGS_ROW_REDUCE")
+    mode = _pinned(_state["row_reduce"], "HGS_ROW_REDUCE")
     if mode is None and not _state["async"]:
         mode = R >= 4 * P
     return 0 if mode is None else (ROWS_REDUCE if mode else ROWS_INLINE)   # (None: the library's rule, R >= 8 P)
@@ -86,13 +88,13 @@ def set_lazy_records(mode):
     HGS_RECORDS_LAZY / HGS_RECORDS_PACKED): True = built from the Gaussians' templates through the sorted keys, False = packed
     by the sort kernel, None = the library's rule (lazy from 128 entries per tile).  Images and gradients are the same bits
     either way.  Returns the previous setting."""
-    was = _state.get("lazy_records")
+    was = _state["lazy_records"]
     _state["lazy_records"] = None if mode is None else bool(mode)
     return was
 
 
 def _records_flags():
-    lazy = _pinned(_state.get("lazy_records"), "HGS_LAZY_RECORDS")
+    lazy = _pinned(_state["lazy_records"], "HGS_LAZY_RECORDS")
     return 0 if lazy is None else (RECORDS_LAZY if lazy else RECORDS_PACKED)   # (None: the library's rule)
 
 
@@ -100,51 +102,101 @@ def set_row_runs(mode):
     """How the preprocess launch counts tile rectangles of more than 16 tiles (include/hgs.h HGS_COUNT_ROW_RUNS): True = by tile
     rows plus a one-workgroup launch, False = tile by tile, None = decide per pass from the instances per Gaussian seen so far
     (capacity mode: the capacity; blocking mode: the previous pass's exact count) -- the counts are the same integers either way."""
-    was = _state.get("row_runs")
+    was = _state["row_runs"]
     _state["row_runs"] = None if mode is None else bool(mode)
     return was
 
 
 def _row_runs_flag(P, use_async):
-    mode = _pinned(_state.get("row_runs"), "HGS_ROW_RUNS")
+    mode = _pinned(_state["row_runs"], "HGS_ROW_RUNS")
     if mode is None:
-        mode = (_state["cap"] if use_async else _state.get("last_exact_R", 0)) >= 8 * P
+        mode = (_state["cap"] if use_async else _state["last_exact_R"]) >= 8 * P
     return COUNT_ROW_RUNS if (mode and P > 0) else 0
 
 
 def set_async(enabled=True, slack=1.5):
-    """Capacity mode: passes never wait for num_rendered; the library keeps a sticky device-side maximum of it
-    (hgs_forward_preprocess max_rendered) which check_async() reads -- one synchronisation per check, no per-pass copy."""
+    """Capacity mode on / off (see the top of the module); clears the pending marks, keeps the learnt capacity."""
     _state["async"], _state["slack"] = bool(enabled), float(slack)
-    _state["dirty"] = False
-    _state["cap_used"] = None
+    _state["dirty"], _state["cap_used"] = False, None
+
+
+@contextlib.contextmanager
+def async_mode(enabled, slack=None):
+    """Run the body in capacity mode (at `slack`, if given) or blocking mode; mode, slack and pending marks are then put back, a capacity learnt inside stays."""
+    saved = {k: _state[k] for k in ("async", "slack", "dirty", "cap_used")}
+    _state["async"], _state["slack"] = bool(enabled), _state["slack"] if slack is None else float(slack)
+    try:
+        yield
+    finally:
+        _state.update(saved)
+
+
+def capacity():
+    """The learnt binning capacity (0: none yet)."""
+    return _state["cap"]
+
+
+def reset_capacity(n=0):
+    """Forget the learnt capacity (the next capacity-mode pass blocks once and learns it anew), or force it to `n`."""
+    _state["cap"] = int(n)
+
+
+def raise_capacity(worst, slack=None):
+    """THE growth rule: the capacity covers slack x `worst` instances (None: the mode's slack) and never shrinks.  Returns it."""
+    slack = _state["slack"] if slack is None else slack
+    _state["cap"] = max(_state["cap"], bucket_capacity(int(worst * slack) + 4096))
+    return _state["cap"]
+
+
+def last_exact_rendered():
+    """The instance COUNT (not a capacity) of the last blocking pass or check_async(): what set_row_reduce's callers decide by."""
+    return _state["last_exact_R"]
+
+
+def last_counts_clean():
+    """Did the last pass leave the per-tile instance counters of its image buffer at zero?  (see _forward)"""
+    return _state["last_counts_clean"]
 
 
 def _max_rendered(dev):
-    t = _state["max_R"].get(dev)
-    if t is None:
-        t = torch.zeros(1, dtype=torch.int32, device=dev)
-        _state["max_R"][dev] = t
-    return t
+    if dev not in _state["max_R"]:
+        _state["max_R"][dev] = torch.zeros(1, dtype=torch.int32, device=dev)
+    return _state["max_R"][dev]
+
+
+def read_max_rendered(word=None):
+    """THE read of a sticky word (None: the worst over this module's, one per device), which it zeroes; nothing else changes."""
+    worst = 0
+    for t in _state["max_R"].values() if word is None else (word,):
+        worst = max(worst, int(t.item()) & 0xFFFFFFFF)   # (.item() synchronises the stream the passes ran on; the word is unsigned)
+        t.zero_()
+    if worst == 0xFFFFFFFF:   # include/hgs.h HGS_WAIT_TIMED_OUT: an error (every word is zeroed by now), never a count
+        raise rt.HgsError("a raster pass gave up an inter-workgroup wait (status word 8): its frame is invalid")
+    return worst
+
+
+def _mark_pending(cap):
+    _state["dirty"], _state["cap_used"] = True, cap if _state["cap_used"] is None else min(_state["cap_used"], cap)
+
+
+def discard_pending():
+    """Zero every word unread and clear the marks; returns the smallest capacity a pass since the last check ran with (or None)."""
+    cap, _state["dirty"], _state["cap_used"] = _state["cap_used"], False, None
+    for t in _state["max_R"].values():
+        t.zero_()
+    return cap
 
 
 def check_async():
     """Synchronise once and validate every pass issued since the last check against the capacity it ran with; returns
     [largest num_rendered seen] ([] if no pass was issued).  Raises HgsCapacityOverflow after raising the capacity."""
-    if not _state.get("dirty"):
+    if not _state["dirty"]:
         return []
-    worst, cap = 0, _state["cap_used"]
-    for t in _state["max_R"].values():
-        worst = max(worst, int(t.item()) & 0xFFFFFFFF)   # (.item() synchronises the stream the passes ran on; the word is unsigned)
-        t.zero_()
-    _state["dirty"] = False
-    _state["cap_used"] = None
-    _state["last_exact_R"] = worst        # (an instance COUNT, not a capacity: what set_row_reduce's callers decide by)
-    if worst == 0xFFFFFFFF:   # include/hgs.h HGS_WAIT_TIMED_OUT
-        raise rt.HgsError("a raster pass gave up an inter-workgroup wait (status word 8): its frame is invalid")
-    _state["cap"] = max(_state["cap"], bucket_capacity(int(worst * _state["slack"]) + 4096))
+    cap, _state["dirty"], _state["cap_used"] = _state["cap_used"], False, None
+    worst = _state["last_exact_R"] = read_max_rendered()
+    raised = raise_capacity(worst)
     if cap is not None and worst > cap:
-        raise HgsCapacityOverflow(f"a raster pass needed {worst} instances (capacity {cap}): capacity raised to {_state['cap']}, repeat the step")
+        raise HgsCapacityOverflow(f"a raster pass needed {worst} instances (capacity {cap}): capacity raised to {raised}, repeat the step")
     return [worst]
 
 
@@ -307,16 +359,14 @@ def _forward(background, means3D, colors, opacity, scales, rotations, scale_modi
             R = int(n_host.value)
             _state["last_exact_R"] = R
             if _state["async"]:  # first call: learn the scale of the scene with one blocking read
-                _state["cap"] = max(_state["cap"], bucket_capacity(int(R * _state["slack"]) + 4096))
+                raise_capacity(R)
         binning = torch.empty((L.hgs_binning_bytes(R, n_ch),), **u8)
         rt.check(L.hgs_forward_render(stream, P, W, H, R, n_ch - 3, _records_flags(), rt.ptr(bg), rt.ptr(colors_),
                                       rt.ptr(extra_), rt.ptr(geom), rt.ptr(binning), rt.ptr(img), rt.ptr(out_color)))
         if use_async and max_rendered is None:
-            _state["dirty"] = True
-            _state["cap_used"] = R if _state["cap_used"] is None else min(_state["cap_used"], R)
+            _mark_pending(R)
         if debug:
             torch.cuda.synchronize(dev)  # surface asynchronous faults here, like CHECK_CUDA (auxiliary.h:166-173)
-    _state["last_R"] = R
     return R, out_color, radii, geom, binning, img
 
 

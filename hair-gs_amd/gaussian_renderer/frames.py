@@ -15,6 +15,7 @@ import functools
 
 import torch
 
+from diff_gaussian_rasterization import _C as raster
 import hgs_runtime as rt
 from hgs_runtime.strand_step import ViewTable
 
@@ -44,7 +45,6 @@ class FrameRenderer:
         self._graph = self._binding = self._key = self._out = None
         self._pending = []          # graph frames enqueued since the last validation
         self._max_R = torch.zeros(1, dtype=torch.int32, device=dev)   # sticky maximum of num_rendered of THIS renderer's frames
-        self._last_R = 0
         self.captures = 0
 
     # ---- one frame on the current stream, current slot view -------------------------------------------------------
@@ -58,7 +58,6 @@ class FrameRenderer:
         """One frame of the current slot view on the current stream.  The Gaussians are what render() hands to the rasterizer,
         bit for bit: strand geometry and opacity from the kernel behind HairGaussianModel.derived_gaussians (which also
         carries the view select as a rider), a cloud's from the model's own getters (captured like any other launch)."""
-        from diff_gaussian_rasterization import _C as raster
         g, vt, L = self.g, self.views, rt.lib()
         dev = vt.device
         f32 = dict(dtype=torch.float32, device=dev)
@@ -83,24 +82,13 @@ class FrameRenderer:
                 self.bg, xyz, self.empty, opacity, scale, quat, 1.0, self.empty, vt.viewmatrix, vt.projmatrix,
                 vt.tanfovx, vt.tanfovy, vt.H, vt.W, shs, int(g.active_sh_degree), vt.campos, own_image, self._max_R, hair)
             if own_image is not None and xyz.shape[0] > 0:
-                vt.counts_clean = raster._state["last_counts_clean"]
-        self._last_R = int(out[0])
+                vt.counts_clean = raster.last_counts_clean()
         return {"render": out[1], "radii": out[2]}
 
     # ---- capture / replay ---------------------------------------------------------------------------------------------
-    def _read_max(self):
-        worst = int(self._max_R.item()) & 0xFFFFFFFF       # (.item() waits for the frames on this stream)
-        self._max_R.zero_()
-        if worst == 0xFFFFFFFF:   # include/hgs.h HGS_WAIT_TIMED_OUT
-            raise rt.HgsError("a raster pass gave up an inter-workgroup wait (status word 8): its frame is invalid")
-        return worst
-
     def _capture(self):
-        from diff_gaussian_rasterization import _C as raster
-        vt, st = self.views, raster._state
-        saved = {k: st[k] for k in ("async", "slack", "dirty", "cap_used")}
-        st["async"], st["slack"] = True, self.slack         # capacity mode for the passes issued below (nothing blocks)
-        try:
+        vt = self.views
+        with raster.async_mode(True, self.slack):            # capacity mode for the passes issued below (nothing blocks)
             s = self._stream = torch.cuda.Stream(device=vt.device)
             s.wait_stream(torch.cuda.current_stream(vt.device))
             with torch.cuda.stream(s):
@@ -109,7 +97,7 @@ class FrameRenderer:
                 for v in sorted({(k * vt.n) // 16 for k in range(16)}):
                     vt.prologue(v, ride=True)
                     self._frame()
-                    st["cap"] = max(st["cap"], raster.bucket_capacity(int(self._read_max() * self.slack) + 4096))
+                    raster.raise_capacity(raster.read_max_rendered(self._max_R), self.slack)
                 ga = torch.cuda.CUDAGraph(keep_graph=True)
                 with torch.cuda.graph(ga, stream=s):
                     vt.prologue(0, ride=True)
@@ -126,9 +114,7 @@ class FrameRenderer:
                     gk.instantiate()
                     self._many = (gk, vt.graph_bind(gk, self.K), outs)
             torch.cuda.current_stream(vt.device).wait_stream(s)
-        finally:
-            st.update(saved)
-        self._graph, self._cap = ga, self._last_R
+        self._graph, self._cap = ga, raster.capacity()   # (what every captured frame was built for)
         self._max_R.zero_()                              # (the capture itself launched nothing)
         self._key = self._model_key()
         self.captures += 1
@@ -138,13 +124,9 @@ class FrameRenderer:
         if not 0 <= int(view) < vt.n:
             raise rt.HgsError(f"view {view} outside the table (0..{vt.n - 1})")
         if not self.use_graph or (self.g.endpoint_pairs if self.hair else self.g._xyz).shape[0] == 0:
-            from diff_gaussian_rasterization import _C as raster
-            was, raster._state["async"] = raster._state["async"], False   # eager: the blocking mode, exact buffer sizes
-            try:
+            with raster.async_mode(False):                   # eager: the blocking mode, exact buffer sizes
                 vt.prologue(int(view), ride=True)
                 self._out = self._frame()
-            finally:
-                raster._state["async"] = was
             return
         if self._graph is None or self._key != self._model_key():
             self._capture()
@@ -158,13 +140,12 @@ class FrameRenderer:
         the capacity the graph was captured for.  Returns the views to render again ([] if every frame is good): which
         frame overflowed is not recorded, so all of them are suspect; the capacity has been raised and the next render()
         captures anew."""
-        from diff_gaussian_rasterization import _C as raster
         pending, self._pending = self._pending, []
         if not pending:
             return []
-        worst = self._read_max()
+        worst = raster.read_max_rendered(self._max_R)       # (waits for the frames on this stream)
         if worst > self._cap:
-            raster._state["cap"] = max(raster._state["cap"], raster.bucket_capacity(int(worst * self.slack) + 4096))
+            raster.raise_capacity(worst, self.slack)
             self._graph = None
             return pending
         return []

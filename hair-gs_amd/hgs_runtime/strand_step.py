@@ -298,7 +298,7 @@ def _raster_head_forward(step, xyz, scale, quat, opacity, extra4, shs, endpoints
         step.bg7, xyz, empty, extra4, opacity, scale, quat, 1.0, empty, vt.viewmatrix, vt.projmatrix, vt.tanfovx,
         vt.tanfovy, vt.H, vt.W, shs, g.active_sh_degree, vt.campos, False, False, image_buffer=own_image, hair=hair)
     if own_image is not None and xyz.shape[0] > 0:
-        vt.counts_clean = raster._state["last_counts_clean"]
+        vt.counts_clean = raster.last_counts_clean()
     hp.n_endpoints = n_endpoints
     # the blend backward reads dL/dimage only on tiles where a pixel blended an entry (the image buffer's per-tile
     # contributor count, written by the forward pass above): the SSIM backward leaves the other blocks alone

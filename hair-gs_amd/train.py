@@ -17,6 +17,7 @@ import random
 import torch
 import torch.distributed as dist
 
+from diff_gaussian_rasterization import _C as raster
 from gaussian_renderer import render
 from loss.losses import loss_function, loss_function_single_pass
 from scene.hair_gaussian_model import HairGaussianModel
@@ -218,22 +219,19 @@ def training_step(gaussians, viewpoint_cam, opt, bg, iteration, extent=1.0, vp=N
     `event_log`: a list that receives one dict per iteration on which a topology operator ran -- the operators' own counts
     (clone / split / merge_collapsed / prune_* / merge, the reference's TrainingInfo.densification_info) and the primitive
     count before and after; asking for it costs the operators one host synchronisation per count."""
-    from diff_gaussian_rasterization import _C as raster
     # once per ITERATION, not per attempt: a repeated attempt (capacity overflow) must not bump the SH degree again
     gaussians.update_learning_rate(iteration)
     if iteration % 1000 == 0:
         gaussians.oneupSHdegree()
     for _attempt in range(4):
         try:
-            return _training_step(gaussians, viewpoint_cam, opt, bg, iteration, extent, vp, raster, fused,
-                                  black_background, event_log)
+            return _training_step(gaussians, viewpoint_cam, opt, bg, iteration, extent, vp, fused, black_background, event_log)
         except raster.HgsCapacityOverflow:
             gaussians.optimizer.zero_grad(set_to_none=True)
     raise RuntimeError("rasterizer capacity kept overflowing")
 
 
-def _training_step(gaussians, viewpoint_cam, opt, bg, iteration, extent, vp, raster, fused=None, black_background=False,
-                   event_log=None):
+def _training_step(gaussians, viewpoint_cam, opt, bg, iteration, extent, vp, fused=None, black_background=False, event_log=None):
     # The reference ends every iteration with zero_grad(set_to_none=True) (train.py:203): an iteration starts without
     # gradients.  A captured graph leaves its static gradient tensors in `.grad` after a replay -- an eager iteration that
     # follows (topology iterations of training(), bench.py's kernel-timing pass) would ACCUMULATE onto them.
@@ -353,6 +351,7 @@ def release_graph_pool(device):
 
 
 _LAST_CAPTURE_CAP = {}
+_RECAPTURE_SLACK = 2.0      # what training() raises the capacity by after a rollback or at 80 % use (not opt.capacity_slack)
 _CAPTURE_STREAMS = {}
 
 
@@ -382,8 +381,7 @@ class GraphedStep:
         sums their gradients; with W ranks the step's gradient is the MEAN over the views_per_step x W views of the
         global batch (strong-scaling protocol: the batch is fixed, the ranks share it)."""
         import copy
-        from diff_gaussian_rasterization import _C as raster
-        self.g, self.opt, self.bg, self.extent, self.raster = gaussians, opt, bg, extent, raster
+        self.g, self.opt, self.bg, self.extent = gaussians, opt, bg, extent
         # the background is a constant of the captured step: looked at once, here, before anything is captured
         self.black_background = bool((bg == 0).all())
         self.vp = vp if vp is not None else ViewParallel()
@@ -508,7 +506,7 @@ class GraphedStep:
 
     def capture(self, warmup_cams, iteration=1):
         """Warm up eagerly on a side stream (allocator, lazy module loads, capacity), then capture."""
-        g, raster = self.g, self.raster
+        g = self.g
         self._make_capturable()
         self._graphs = None            # (load_camera launches the prologue until the new graph exists)
         saved_stats = (g.max_radii2D.clone(), g.xyz_gradient_accum.clone(), g.denom.clone())  # warm-up must not count
@@ -532,7 +530,7 @@ class GraphedStep:
                     raster.check_async()        # learns the capacity; an overflow here only raises it for the capture
                 except raster.HgsCapacityOverflow:
                     pass
-                warm_R = max(warm_R, int(raster._state.get("last_exact_R", 0)) & 0x7FFFFFFF)
+                warm_R = max(warm_R, raster.last_exact_rendered())
         # how the single-pass backward sums its instance rows (include/hgs.h HGS_ROWS_REDUCE) follows the MODEL: the instance
         # counts the warm-up has just measured, not the capacity -- for this capture, its replays and the eager iterations until
         # the next capture (every rank sees the same model and the same warm-up views)
@@ -540,7 +538,7 @@ class GraphedStep:
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         g.optimizer.zero_grad(set_to_none=True)
-        if _LAST_CAPTURE_CAP.get(dev_key) not in (None, raster._state["cap"]):
+        if _LAST_CAPTURE_CAP.get(dev_key) not in (None, raster.capacity()):
             # the capacity (as the warm-up has just settled it) is in another bucket than the previous capture's: nothing the
             # allocator has cached for the old one fits any more.  Handing it back costs the next passes their hipMallocs
             # (tens of ms per event: tools/soak.py 2.4 -> 3.1 s when done at every bucket change), so it waits until the
@@ -620,12 +618,8 @@ class GraphedStep:
             self.fused.enable_inline_adam(False)      # (the graphs keep what they captured; eager users of these views do not inherit it)
         # every replay raises the library's sticky device-side maximum of num_rendered; check() compares it with the
         # capacity the captured passes were built for
-        self._cap = raster._state["cap_used"]
-        _LAST_CAPTURE_CAP[dev_key] = raster._state["cap"]
-        for t in raster._state["max_R"].values():
-            t.zero_()                       # the capture itself launched nothing
-        raster._state["dirty"] = False
-        raster._state["cap_used"] = None
+        self._cap = raster.discard_pending()          # (the capture itself launched nothing)
+        _LAST_CAPTURE_CAP[dev_key] = raster.capacity()
 
     def step(self, cam, iteration):
         """One optimizer step on `cam` (views_per_step > 1: on the list of this rank's views of the global batch);
@@ -670,19 +664,11 @@ class GraphedStep:
     def headroom(self):
         """(largest num_rendered of the replays since the last check, captured capacity): one synchronisation, no
         exception -- lets a long run re-capture BEFORE a growing model overflows the captured binning capacity."""
-        raster = self.raster
-        worst = 0
-        for t in raster._state["max_R"].values():
-            worst = max(worst, int(t.item()) & 0xFFFFFFFF)   # (the word is unsigned)
-            t.zero_()
-        if worst == 0xFFFFFFFF:   # include/hgs.h HGS_WAIT_TIMED_OUT
-            raise self.raster.rt.HgsError("a replayed raster pass gave up an inter-workgroup wait: its frame is invalid")
-        return worst, self._cap
+        return raster.read_max_rendered(), self._cap
 
     def check(self):
         """Synchronise and validate the instance counts of ALL replays since the last check (raises on capacity
         overflow); returns [largest num_rendered seen]."""
-        raster = self.raster
         worst, _ = self.headroom()
         if self._cap is not None and worst > self._cap:
             raise raster.HgsCapacityOverflow(
@@ -757,11 +743,10 @@ def training(gaussians, cameras, opt, iterations=None, extent=1.0, seed=0, log_e
         """A replayed pass needed more instances than the graph was captured for: its gradients were zero (include/hgs.h),
         so the steps since the last check are not what the reference computes (train.py:146-204: every step has its
         gradient).  Return to the checkpoint, raise the capacity and run those iterations again."""
-        from diff_gaussian_rasterization import _C as raster
         if vp.rank == 0:
             print(f"[it {it_now}] binning capacity {cap} exceeded ({worst} instances): iterations {ckpt.it + 1}..{it_now} "
                   "are run again from the last checkpoint with a larger capacity")
-        raster._state["cap"] = max(raster._state["cap"], raster.bucket_capacity(int(worst * 2.0) + 4096))
+        raster.raise_capacity(worst, _RECAPTURE_SLACK)
         return ckpt.restore(gaussians, sampler)
 
     try:
@@ -826,17 +811,14 @@ def training(gaussians, cameras, opt, iterations=None, extent=1.0, seed=0, log_e
                     continue
                 ckpt.take(gaussians, sampler, ema, it - 1)
                 if cap is not None and worst > 0.8 * cap:
-                    from diff_gaussian_rasterization import _C as raster
-                    raster._state["cap"] = max(raster._state["cap"], raster.bucket_capacity(int(worst * 2.0) + 4096))
+                    raster.raise_capacity(worst, _RECAPTURE_SLACK)
                     gs = None
             if log_every and vp.rank == 0 and any(j % log_every == 0 for j in range(first, it)):
                 print(f"[it {it - 1}] loss(ema) {float(ema):.6f}  segments {gaussians.get_xyz.shape[0]}")
     finally:
         if use_graph:
-            from diff_gaussian_rasterization import _C as raster
             raster.set_async(False)
             raster.set_row_reduce(None)       # (what the captures of this run chose: back to the per-call default)
-    training.last_void_steps = 0          # (kept for callers of earlier rounds: overflowed steps are now run again)
     training.last_rollbacks = rollbacks
     return ema
 

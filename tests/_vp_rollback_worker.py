@@ -24,7 +24,7 @@ def main():
 
     def run(slack, iterations):
         safe_state(True)
-        raster._state["cap"] = 0
+        raster.reset_capacity(0)
         model = make_strand_model(300, 40, device="cuda", spatial_lr_scale=extent)
         model.compute_strands_info(only_foreground=True)
         attach_targets(cams, model)

@@ -74,7 +74,7 @@ def test_frame_renderer_unchecked_frames_and_capacity():
     from gaussian_renderer import render
     from gaussian_renderer.frames import FrameRenderer
     model, cams, bg = _setup("hair")
-    mode_before = raster._state["async"]
+    raster.set_async(False)                                        # the module's mode before: blocking
     fr = FrameRenderer(model, cams, bg, slack=1.0)
     imgs = [fr.render(i, check=False)["render"].clone() for i in range(len(cams))]
     assert fr.validate() == []
@@ -96,7 +96,8 @@ def test_frame_renderer_unchecked_frames_and_capacity():
     out = fr.render(2)                                             # a checked render repairs an overflow by itself
     with torch.no_grad():
         assert torch.equal(out["render"], render(cams[2], model, bg)["render"])
-    assert raster._state["async"] is mode_before                  # the module's mode is as it was
+    # the module's mode is as it was: a capacity is learnt by now, so in capacity mode that render() would be pending
+    assert raster.check_async() == []
 
 
 def test_view_table_without_targets_is_refused_by_the_training_step():

@@ -440,18 +440,24 @@ def test_wait_timeout_word_is_not_silent():
     import torch
     import hgs_runtime as rt
     from diff_gaussian_rasterization import _C as raster
+    from tests import gpu_util as G
+    cap_at_entry = raster.capacity()
     raster.set_async(True)
     try:
         dev = torch.device("cuda", torch.cuda.current_device())
+        s = _scene("sh0")
+        G.run_forward(s)                    # (learns a capacity if there is none)
+        G.run_forward(s)                    # a capacity-mode pass: pending until the next check
         word = raster._max_rendered(dev)
         word.fill_(-1)                      # int32 -1 == 0xFFFFFFFF, what hgs_wait_parts leaves behind
-        raster._state["dirty"] = True
-        cap_before = raster._state["cap"]
+        cap_before = raster.capacity()
         with pytest.raises(rt.HgsError, match="inter-workgroup wait"):
             raster.check_async()
-        assert raster._state["cap"] == cap_before and int(word.item()) == 0
+        assert raster.capacity() == cap_before and int(word.item()) == 0
+        assert raster.check_async() == []   # the marks went with the error
     finally:
         raster.set_async(False)
+        raster.reset_capacity(cap_at_entry)
 
 
 def test_capacity_overflow_gives_zero_gradients_not_garbage(monkeypatch):
@@ -475,18 +481,18 @@ def test_capacity_overflow_gives_zero_gradients_not_garbage(monkeypatch):
             dpix = np.random.default_rng(4).normal(size=(3, s["H"], s["W"])).astype(np.float32)
             try:
                 _C.set_async(True)
-                _C._state["cap"] = max(64, full["R"] // 3)
+                _C.reset_capacity(max(64, full["R"] // 3))
                 fw = G.run_forward(s)
-                assert fw["R"] == _C._state["cap"] and G.intermediates(s, fw)["status"][1] == 1
+                assert fw["R"] == _C.capacity() and G.intermediates(s, fw)["status"][1] == 1
                 g = G.run_backward(s, fw, dpix)
                 for k, v in g.items():
                     assert np.isfinite(v).all() and (v == 0).all(), k
                 with pytest.raises(_C.HgsCapacityOverflow):
                     _C.check_async()
-                assert _C._state["cap"] > full["R"]
+                assert _C.capacity() > full["R"]
             finally:
                 _C.set_async(False)
-                _C._state["cap"] = 0
+                _C.reset_capacity(0)
             # and the same scene right after, with enough capacity, is unaffected
             g2 = G.run_backward(s, full, dpix)
             assert any((v != 0).any() for v in g2.values())
@@ -531,7 +537,7 @@ def test_capacity_mode_binning_equals_blocking_mode(name):
     ref_fw = G.run_forward(s)
     ref = G.intermediates(s, ref_fw)
     try:
-        _C._state["cap"] = 0                   # (a capacity learnt on another scene would be kept)
+        _C.reset_capacity(0)                   # (a capacity learnt on another scene would be kept)
         _C.set_async(True)
         G.run_forward(s)                       # the first pass of the mode learns the capacity (it blocks)
         fw = G.run_forward(s)                  # capacity mode
@@ -1209,7 +1215,7 @@ def test_row_run_counting_changes_nothing(name):
         if ref["num_rendered"] == 0:
             return
         try:
-            _C._state["cap"] = 0
+            _C.reset_capacity(0)
             _C.set_async(True)
             G.run_forward(s)
             for _ in range(2):
@@ -1255,7 +1261,7 @@ def test_lazy_records_change_nothing(name):
             np.testing.assert_array_equal(runs[0][1][k].view(np.uint32), runs[1][1][k].view(np.uint32), err_msg=k)
         if runs[0][0]["num_rendered"] == 0:
             return
-        _C._state["cap"] = 0
+        _C.reset_capacity(0)
         _C.set_async(True)
         G.run_forward(s)
         for lazy in (0, 1):

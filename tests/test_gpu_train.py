@@ -258,17 +258,17 @@ def test_async_capacity_mode_matches_blocking_and_recovers_from_overflow():
         for a, b in zip(got, ref):
             assert torch.equal(a, b)
         # force an overflow: shrink the capacity below what the scene needs
-        raster._state["cap"] = 64
+        raster.reset_capacity(64)
         with torch.no_grad():
             render(cams[0], model, bg)
         with pytest.raises(raster.HgsCapacityOverflow):
             raster.check_async()
-        assert raster._state["cap"] > 64
+        assert raster.capacity() > 64
         # training_step repeats the step transparently
         opt = OptimizationParams()
         opt.enable_topology = False
         model.training_setup(opt)
-        raster._state["cap"] = 64
+        raster.reset_capacity(64)
         before = model._endpoints.detach().clone()
         loss, _, _ = training_step(model, cams[1], opt, bg, 1, extent=extent)
         assert torch.isfinite(loss) and not torch.equal(before, model._endpoints.detach())
@@ -276,9 +276,9 @@ def test_async_capacity_mode_matches_blocking_and_recovers_from_overflow():
         # (every 1000th, train.py:136-137) bumps it once (round 3 bumped it per attempt and skipped a degree)
         bumps = []
         model.oneupSHdegree = lambda: bumps.append(1)
-        raster._state["cap"] = 64
+        raster.reset_capacity(64)
         training_step(model, cams[2], opt, bg, 1000, extent=extent)
-        assert raster._state["cap"] > 64 and len(bumps) == 1
+        assert raster.capacity() > 64 and len(bumps) == 1
     finally:
         raster.set_async(False)
 
@@ -588,7 +588,7 @@ def test_capacity_overflow_mid_run_is_rolled_back_exactly(capsys, monkeypatch):
     extent = cameras_extent(cams)
 
     def run(slack, iterations, widen_at=None):
-        raster._state["cap"] = 0
+        raster.reset_capacity(0)
         model = make_strand_model(300, 40, device="cuda", spatial_lr_scale=extent)
         model.compute_strands_info(only_foreground=True)
         attach_targets(cams, model)
@@ -630,7 +630,7 @@ def test_capacity_overflow_mid_run_is_rolled_back_exactly(capsys, monkeypatch):
         for a, b in zip(small2, roomy2):
             assert torch.equal(a, b)
     finally:
-        raster._state["cap"] = 0
+        raster.reset_capacity(0)
         raster.set_async(False)
 
 
@@ -1563,12 +1563,11 @@ def test_replays_after_a_blocking_pass_on_the_same_views():
                 gs.step(cams[ci], it)
             if disturb:
                 torch.cuda.synchronize()
-                raster._state["async"] = False                      # a blocking pass through the same table and image buffer
-                probe = fused_step_for(model, views, opt, bg)
-                views.prologue(2, ride=True)
-                with torch.no_grad():
-                    probe.loss()
-                raster._state["async"] = True
+                with raster.async_mode(False):                      # a blocking pass through the same table and image buffer
+                    probe = fused_step_for(model, views, opt, bg)
+                    views.prologue(2, ride=True)
+                    with torch.no_grad():
+                        probe.loss()
                 assert not views.counts_clean
             for it, ci in enumerate([2, 1, 0], 4):
                 gs.step(cams[ci], it)
@@ -1802,7 +1801,7 @@ def test_row_run_counting_in_the_fused_iterations(kind):
     out = {}
     was = raster.set_row_runs(False)
     try:
-        raster._state["cap"] = 0
+        raster.reset_capacity(0)
         raster.set_async(True, slack=2.0)
         for rows in (False, True):
             raster.set_row_runs(rows)
@@ -1903,7 +1902,7 @@ def test_lazy_records_in_the_fused_iterations(kind):
     out = {}
     was = raster.set_lazy_records(None)
     try:
-        raster._state["cap"] = 0
+        raster.reset_capacity(0)
         raster.set_async(True, slack=2.0)
         for lazy in (0, 1):
             raster.set_lazy_records(lazy)

@@ -2,6 +2,7 @@
 table the topology operators ask in place of torch.unique + torch.isin, the first-occurrence mask of
 remove_duplicate_endpoint_rows, and the tile-order view of a capacity-mode binning buffer used by the parity tests."""
 import numpy as np
+import pytest
 import torch
 
 
@@ -83,6 +84,147 @@ def test_bucket_capacity_keeps_four_significant_bits():
         assert n <= 16 or bin(c).rstrip("0").count("1") <= 4 and len(bin(c).rstrip("0")) - 2 <= 4
         prev = c
     assert len({b(n) for n in range(100000, 112000)}) <= 2
+
+
+@pytest.fixture
+def raster_word():
+    """(diff_gaussian_rasterization._C in blocking mode with no capacity and nothing pending, a CPU int32 tensor as its sticky word)."""
+    from diff_gaussian_rasterization import _C as raster
+    cap = raster.capacity()
+    raster.set_async(False)
+    raster.reset_capacity(0)
+    word = raster._max_rendered(torch.device("cpu"))
+    raster.discard_pending()
+    yield raster, word
+    raster.set_async(False)
+    raster.discard_pending()
+    raster.reset_capacity(cap)
+
+
+def test_capacity_growth_rule(raster_word):
+    """raise_capacity is the one growth rule: bucket_capacity(int(worst * slack) + 4096), never shrinking; check_async() applies it
+    with the mode's slack whether or not a pass overflowed, and records the worst count as the last exact one."""
+    raster, word = raster_word
+    raster.set_async(True, slack=1.5)
+    raster._mark_pending(1 << 20)
+    word.fill_(100000)
+    assert raster.check_async() == [100000]                       # no overflow, and still ...
+    assert raster.capacity() == raster.bucket_capacity(154096) == 163840
+    assert raster.last_exact_rendered() == 100000
+    raster._mark_pending(1 << 20)
+    word.fill_(50000)
+    assert raster.check_async() == [50000] and raster.capacity() == 163840      # a smaller worst leaves it
+    assert raster.raise_capacity(10) == 163840
+    assert raster.raise_capacity(100000, 2.0) == raster.bucket_capacity(204096) == raster.capacity() > 163840
+    raster.reset_capacity(0)
+    assert raster.capacity() == 0                                 # forgotten
+    assert raster.raise_capacity(100000) == 163840                # slack None: the mode's
+    raster.reset_capacity(64)
+    assert raster.capacity() == 64                                # forced
+
+
+def test_check_async_overflow_is_worst_above_the_smallest_capacity_used(raster_word):
+    raster, word = raster_word
+    raster.set_async(True, slack=1.5)
+    assert raster.check_async() == []                             # nothing pending: the word is not even looked at
+    word.fill_(77)
+    assert raster.check_async() == [] and int(word.item()) == 77
+    word.zero_()
+    for worst, overflows in ((100000, False), (100001, True)):
+        raster.reset_capacity(0)
+        raster._mark_pending(200000)
+        raster._mark_pending(100000)                              # the smallest capacity used counts
+        raster._mark_pending(150000)
+        word.fill_(worst)
+        if overflows:
+            with pytest.raises(raster.HgsCapacityOverflow, match="needed 100001 instances .capacity 100000."):
+                raster.check_async()
+        else:
+            assert raster.check_async() == [worst]
+        assert raster.capacity() == raster.bucket_capacity(int(worst * 1.5) + 4096)     # raised either way
+        assert raster.last_exact_rendered() == worst
+        assert int(word.item()) == 0 and raster.check_async() == []                    # word zeroed, marks cleared
+
+
+def test_timeout_sentinel_is_an_error_and_never_a_capacity(raster_word):
+    """HGS_WAIT_TIMED_OUT (include/hgs.h) in a sticky word: HgsError from every reader, the word zeroed, the capacity as it was."""
+    import hgs_runtime as rt
+    raster, word = raster_word
+    raster.set_async(True)
+    raster.reset_capacity(4096)
+    raster._mark_pending(4096)
+    word.fill_(-1)                                                # int32 -1 == 0xFFFFFFFF
+    with pytest.raises(rt.HgsError, match="inter-workgroup wait"):
+        raster.check_async()
+    assert raster.capacity() == 4096 and int(word.item()) == 0
+    assert raster.check_async() == []                             # the marks were cleared before it raised
+    own = torch.full((1,), -1, dtype=torch.int32)                 # a caller's own word (FrameRenderer's)
+    with pytest.raises(rt.HgsError, match="inter-workgroup wait"):
+        raster.read_max_rendered(own)
+    assert int(own.item()) == 0 and raster.capacity() == 4096
+    word.fill_(-1)                                                # GraphedStep.headroom's read
+    with pytest.raises(rt.HgsError, match="inter-workgroup wait"):
+        raster.read_max_rendered()
+    assert int(word.item()) == 0 and raster.capacity() == 4096
+    own.fill_(-2)                                                 # the word is unsigned: a count above 2^31 is a count
+    assert raster.read_max_rendered(own) == 0xFFFFFFFE
+
+
+def test_discard_pending_and_the_headroom_read(raster_word):
+    """What GraphedStep.capture ends with and what GraphedStep.headroom reads."""
+    raster, word = raster_word
+    raster.set_async(True, slack=1.5)
+    raster.reset_capacity(8192)
+    assert raster.discard_pending() is None                       # no pass since the last check
+    raster._mark_pending(8192)
+    raster._mark_pending(6144)
+    word.fill_(999999)                                            # (would be an overflow if it were read)
+    assert raster.discard_pending() == 6144
+    assert int(word.item()) == 0 and raster.check_async() == [] and raster.capacity() == 8192
+    # the headroom read: the worst count, the word zeroed -- capacity, pending marks and last exact count untouched
+    exact = raster.last_exact_rendered()
+    raster._mark_pending(8192)
+    word.fill_(7000)
+    assert raster.read_max_rendered() == 7000 and int(word.item()) == 0
+    assert raster.capacity() == 8192 and raster.last_exact_rendered() == exact
+    word.fill_(9000)
+    with pytest.raises(raster.HgsCapacityOverflow):                # still pending, still against 8192
+        raster.check_async()
+
+
+def test_async_mode_restores_mode_slack_and_marks_and_keeps_the_capacity(raster_word):
+    raster, word = raster_word
+    fuses = lambda: raster.will_fuse_hair(16, 16)                 # (capacity mode and a learnt capacity)
+    for before in (False, True):
+        raster.reset_capacity(8192)
+        raster.set_async(before, slack=3.0)
+        raster._mark_pending(8192)
+        try:
+            with raster.async_mode(not before, slack=1.5):
+                assert fuses() is (not before)
+                raster._mark_pending(16)                          # (a pass of the body's; its mark goes with the body)
+                assert raster.raise_capacity(100000) == 163840    # the body's slack
+                raise KeyError("body")
+        except KeyError:
+            pass
+        assert fuses() is before and raster.capacity() == 163840   # the mode is back, the capacity learnt inside is kept
+        assert raster.raise_capacity(100000) == raster.bucket_capacity(304096)       # the slack is back
+        word.fill_(8192)
+        assert raster.check_async() == [8192]                     # pending as before, against 8192 and not 16
+        with raster.async_mode(True):                             # no slack given: the mode's stays
+            assert fuses() and raster.raise_capacity(200000) == raster.bucket_capacity(604096)
+        assert fuses() is before and raster.check_async() == []
+
+
+def test_set_async_keeps_the_capacity_and_clears_the_marks(raster_word):
+    raster, word = raster_word
+    raster.set_async(True, slack=1.5)
+    raster.reset_capacity(12288)
+    raster._mark_pending(64)
+    raster.set_async(True, slack=2.0)
+    assert raster.capacity() == 12288 and raster.check_async() == []
+    raster.set_async(False)
+    assert raster.capacity() == 12288 and not raster.will_fuse_hair(16, 16)
 
 
 def test_training_event_log_and_visible_gpus_need_no_gpu():
