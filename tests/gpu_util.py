@@ -114,6 +114,54 @@ def blend_work_list(scene, fw):
     return _view(fw["img"], lay["tile_order"], T + max(T, 1024), np.uint32)
 
 
+def loss_head_inputs(H, W, rnd):
+    """Inputs of the loss head's per-pixel terms (mask logits, direction image and their targets) drawn with `rnd(*shape)`, a
+    uniform [0, 1) source on the GPU: the SSIM / L1 tests of the head need them present, not special."""
+    mask_img, omap = rnd(H, W) * 4 - 2, rnd(3, H, W)
+    fmask, ori, conf = (rnd(H, W) > 0.5).float(), rnd(H, W) * 3.14159, rnd(H, W)
+    m8 = (rnd(H, W) > 0.3).to(torch.uint8)
+    return dict(mask_img=mask_img, omap=omap, float_mask=fmask, orientation=ori, confidence=conf, mask=m8)
+
+
+def run_loss_head(image, gt, aux, tile_used=None, fill=7.0):
+    """hgs_loss_head_forward + _backward (upstream gradient 1) on a [3, H, W] render and a device-resident target row built
+    around `gt` and loss_head_inputs(); `tile_used`: int32 [tiles_y, tiles_x] hint of the consumer, or None.  d_image starts as
+    `fill` everywhere.  Returns the head's outputs, the three gradient images and the SSIM backward's block lists
+    (white box: [n_work, n_skip, -, -][work ids][skipped ids] close the scratch buffer)."""
+    import ctypes as C
+    from arguments import OptimizationParams
+    from hgs_runtime.strand_step import head_params
+    dev = image.device
+    H, W = image.shape[-2:]
+    row = rt.ViewTargets()
+    row.image, row.float_mask, row.orientation, row.confidence, row.mask = (
+        t.data_ptr() for t in (gt, aux["float_mask"], aux["orientation"], aux["confidence"], aux["mask"]))
+    for k, v in enumerate(np.eye(4, dtype=np.float32).reshape(-1)):
+        row.viewmatrix[k] = row.projmatrix[k] = float(v)
+    row.mask_count = float(aux["mask"].sum().item())
+    targets = torch.from_numpy(np.frombuffer(bytes(row), dtype=np.uint8).copy()).to(dev)
+    opt = OptimizationParams()
+    hp = head_params(H, W, opt, 0, 0, 1e-6, True)
+    if tile_used is not None:
+        hp.tile_used, hp.tiles_x, hp.tiles_y = tile_used.data_ptr(), tile_used.shape[1], tile_used.shape[0]
+    L = rt.lib()
+    scratch = torch.empty(L.hgs_loss_head_scratch_floats(C.byref(hp)), device=dev)
+    out = torch.zeros(rt.HEAD_NOUT, device=dev)
+    d_img, d_mask, d_omap = torch.full((3, H, W), fill, device=dev), torch.empty(H, W, device=dev), torch.empty(3, H, W, device=dev)
+    one = torch.ones(1, device=dev)
+    mask_img, omap = aux["mask_img"], aux["omap"]
+    rt.check(L.hgs_loss_head_forward(rt.current_stream(), C.byref(hp), image.data_ptr(), mask_img.data_ptr(), omap.data_ptr(),
+                                     targets.data_ptr(), None, None, scratch.data_ptr(), out.data_ptr(), None, None))
+    rt.check(L.hgs_loss_head_backward(rt.current_stream(), C.byref(hp), image.data_ptr(), mask_img.data_ptr(), omap.data_ptr(),
+                                      targets.data_ptr(), None, None, scratch.data_ptr(), out.data_ptr(), one.data_ptr(), 0,
+                                      d_img.data_ptr(), d_mask.data_ptr(), d_omap.data_ptr(), None))
+    nbs = 3 * ((H + 31) // 32) * ((W + 31) // 32)
+    lists = scratch.view(torch.int32)[scratch.numel() - (2 * nbs + 16):].cpu()     # (4 header words, 2 nbs ids, 12 spare)
+    n_work, n_skip = int(lists[0]), int(lists[1])
+    return dict(out=out, terms=dict(zip(rt.HEAD_OUT, out.tolist())), d_image=d_img, d_mask=d_mask, d_omap=d_omap, opt=opt,
+                nbs=nbs, n_work=n_work, n_skip=n_skip, work=lists[4:4 + n_work], skipped=lists[4 + nbs:4 + nbs + n_skip])
+
+
 def free_port():
     """A TCP port nobody listens on right now (rendezvous of the multi-process tests: fixed numbers collide with whatever else
     runs on the box, or with the previous test's socket)."""

@@ -1110,12 +1110,8 @@ def test_loss_head_skips_all_zero_blocks_exactly(hw):
     backward: blocks whose 3x3 block neighbourhood is zero are only zero-filled, the rest is split evenly over the XCDs
     through a compacted list).  The result has to be what the stand-alone hgs_ssim_l1_* kernels (which walk every block)
     produce, and the block lists have to partition the frame."""
-    import ctypes as C
-    import numpy as np
-    import hgs_runtime as rt
-    from arguments import OptimizationParams
     from hgs_runtime.fused import ssim_l1
-    from hgs_runtime.strand_step import head_params
+    from tests import gpu_util as G
     H, W = hw
     dev = torch.device("cuda")
     g = torch.Generator(device="cuda").manual_seed(11)
@@ -1124,41 +1120,21 @@ def test_loss_head_skips_all_zero_blocks_exactly(hw):
     y0, y1, x0, x1 = H // 3, H // 3 + H // 4, W // 4, W // 4 + W // 5
     image[:, y0:y1, x0:x1] = rnd(3, y1 - y0, x1 - x0)
     gt[:, y0 + 2:y1 + 2, x0 - 3:x1 - 3] = rnd(3, y1 - y0, x1 - x0)
-    mask_img, omap = rnd(H, W) * 4 - 2, rnd(3, H, W)
-    fmask, ori, conf = (rnd(H, W) > 0.5).float(), rnd(H, W) * 3.14159, rnd(H, W)
-    m8 = (rnd(H, W) > 0.3).to(torch.uint8)
-    row = rt.ViewTargets()
-    row.image, row.float_mask, row.orientation, row.confidence, row.mask = (t.data_ptr() for t in (gt, fmask, ori, conf, m8))
-    for k, v in enumerate(np.eye(4, dtype=np.float32).reshape(-1)):
-        row.viewmatrix[k] = row.projmatrix[k] = float(v)
-    row.mask_count = float(m8.sum().item())
-    targets = torch.from_numpy(np.frombuffer(bytes(row), dtype=np.uint8).copy()).to(dev)
-    opt = OptimizationParams()
-    hp = head_params(H, W, opt, 0, 0, 1e-6, True)
-    L = rt.lib()
-    scratch = torch.empty(L.hgs_loss_head_scratch_floats(C.byref(hp)), device=dev)
-    out = torch.zeros(rt.HEAD_NOUT, device=dev)
-    d_img, d_mask, d_omap = torch.full((3, H, W), 7.0, device=dev), torch.empty(H, W, device=dev), torch.empty(3, H, W, device=dev)
-    one = torch.ones(1, device=dev)
-    rt.check(L.hgs_loss_head_forward(rt.current_stream(), C.byref(hp), image.data_ptr(), mask_img.data_ptr(), omap.data_ptr(),
-                                     targets.data_ptr(), None, None, scratch.data_ptr(), out.data_ptr(), None, None))
-    rt.check(L.hgs_loss_head_backward(rt.current_stream(), C.byref(hp), image.data_ptr(), mask_img.data_ptr(), omap.data_ptr(),
-                                      targets.data_ptr(), None, None, scratch.data_ptr(), out.data_ptr(), one.data_ptr(), 0,
-                                      d_img.data_ptr(), d_mask.data_ptr(), d_omap.data_ptr(), None))
+    aux = G.loss_head_inputs(H, W, rnd)
+    head = G.run_loss_head(image, gt, aux)
+    out, d_img, opt = head["out"], head["d_image"], head["opt"]
     # stand-alone kernels: every block is filtered
     a = image.clone().requires_grad_(True)
     s, l1 = ssim_l1(a, gt)
     ((1.0 - opt.lambda_dssim) * l1 + opt.lambda_dssim * (1.0 - s)).backward()
-    o = dict(zip(rt.HEAD_OUT, out.tolist()))
+    o = head["terms"]
     assert abs(o["l1"] - float(l1)) <= 1e-6 * max(float(l1), 1e-6)
     assert abs(o["dssim"] - float(1.0 - s)) <= 2e-6
     assert torch.equal(d_img, a.grad)
-    # block lists (white box: [n_work, n_skip, -, -][work ids][skipped ids] close the scratch buffer)
-    nbs = 3 * ((H + 31) // 32) * ((W + 31) // 32)
-    lists = scratch.view(torch.int32)[scratch.numel() - (2 * nbs + 16):].cpu()     # (4 header words, 2 nbs ids, 12 spare)
-    n_work, n_skip = int(lists[0]), int(lists[1])
+    # block lists
+    nbs, n_work, n_skip, work, skipped = (head[k] for k in ("nbs", "n_work", "n_skip", "work", "skipped"))
+    assert nbs == 3 * ((H + 31) // 32) * ((W + 31) // 32)
     assert n_work + n_skip == nbs
-    work, skipped = lists[4:4 + n_work], lists[4 + nbs:4 + nbs + n_skip]
     assert sorted(work.tolist() + skipped.tolist()) == list(range(nbs))
     assert work.tolist() == sorted(work.tolist())
     if (H, W) == (200, 328):
@@ -1174,23 +1150,16 @@ def test_loss_head_skips_all_zero_blocks_exactly(hw):
     used[:, -1] = True                                   # (the odd last column / row matter)
     used[-1, :] = ~used[-1, :]
     tile_used = (used.to(torch.int32) * 5).contiguous()
-    hp.tile_used, hp.tiles_x, hp.tiles_y = tile_used.data_ptr(), tx_n, ty_n
-    d2 = torch.full((3, H, W), 7.0, device=dev)
-    out2 = torch.zeros(rt.HEAD_NOUT, device=dev)
-    rt.check(L.hgs_loss_head_forward(rt.current_stream(), C.byref(hp), image.data_ptr(), mask_img.data_ptr(), omap.data_ptr(),
-                                     targets.data_ptr(), None, None, scratch.data_ptr(), out2.data_ptr(), None, None))
-    rt.check(L.hgs_loss_head_backward(rt.current_stream(), C.byref(hp), image.data_ptr(), mask_img.data_ptr(), omap.data_ptr(),
-                                      targets.data_ptr(), None, None, scratch.data_ptr(), out2.data_ptr(), one.data_ptr(), 0,
-                                      d2.data_ptr(), d_mask.data_ptr(), d_omap.data_ptr(), None))
+    hinted = G.run_loss_head(image, gt, aux, tile_used=tile_used)
+    out2, d2 = hinted["out"], hinted["d_image"]
     assert torch.equal(out2[:14], out[:14])
     # a block is read iff one of its 2 x 2 tiles is
     bu = torch.nn.functional.max_pool2d(torch.nn.functional.pad(used.float(), (0, tx_n % 2, 0, ty_n % 2))[None, None], 2)[0, 0] > 0
     px_used = bu.repeat_interleave(32, dim=0).repeat_interleave(32, dim=1)[:H, :W]
     assert torch.equal(d2[:, px_used], a.grad[:, px_used])            # read blocks: the full result (zero-filled where it is zero)
     assert bool((d2[:, ~px_used] == 7.0).all())                        # the others: untouched
-    lists2 = scratch.view(torch.int32)[scratch.numel() - (2 * nbs + 16):].cpu()
     read_blocks = int(bu.sum()) * 3
-    assert int(lists2[0]) + int(lists2[1]) == read_blocks and int(lists2[0]) <= n_work
+    assert hinted["n_work"] + hinted["n_skip"] == read_blocks and hinted["n_work"] <= n_work
 
 
 def test_one_launch_parameters_and_preprocess_equals_two_launches():
