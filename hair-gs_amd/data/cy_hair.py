@@ -3,7 +3,7 @@
 Layout, little-endian: a 128-byte header "<4sIIIIff3f88s" = signature "HAIR", hair count, point count, array bits, default
 segment count, default thickness, default transparency, default colour (3 floats), 88 bytes of information text; then, in this
 order and only where its bit is set: segments (uint16 per hair, bit 1), points (3 float32 per point, bit 2), thickness (float32
-per point, bit 4), transparency (float32 per point, bit 8), colours (3 float32 per point, bit 16).  Only reading is needed here."""
+per point, bit 4), transparency (float32 per point, bit 8), colours (3 float32 per point, bit 16)."""
 import struct
 from typing import NamedTuple, Optional
 
@@ -63,15 +63,20 @@ def read_cy_hair(path):
     return CYHair(header, seg, pts, th, tr, col)
 
 
-def write_cy_hair(path, points, segments=None, colors=None, d_segments=0, info=""):
-    """Writes a .hair file (segments, points and optional colours): a fixture helper for tests and tools."""
+def write_cy_hair(path, points, segments=None, colors=None, d_segments=0, info="", thickness=None, transparency=None):
+    """Writes a .hair file: segments, points and the optional per-point thickness, transparency and colours, in the format's order
+    (the fixture helper of the tests and tools, and what data/strand_files.py exports through)."""
     points = np.asarray(points, "<f4").reshape(-1, 3)
     nh = len(segments) if segments is not None else (points.shape[0] // (d_segments + 1) if d_segments else 0)
-    arrays = POINTS_BIT | (SEGMENTS_BIT if segments is not None else 0) | (COLORS_BIT if colors is not None else 0)
+    arrays = POINTS_BIT | (SEGMENTS_BIT if segments is not None else 0) | (COLORS_BIT if colors is not None else 0) \
+        | (THICKNESS_BIT if thickness is not None else 0) | (TRANSPARENCY_BIT if transparency is not None else 0)
     with open(path, "wb") as fh:
         fh.write(HEADER.pack(b"HAIR", nh, points.shape[0], arrays, d_segments, 1.0, 0.0, 1.0, 1.0, 1.0, info.encode("ascii")))
         if segments is not None:
             fh.write(np.asarray(segments, "<u2").tobytes())
         fh.write(points.tobytes())
+        for per_point in (thickness, transparency):
+            if per_point is not None:
+                fh.write(np.asarray(per_point, "<f4").reshape(points.shape[0]).tobytes())
         if colors is not None:
             fh.write(np.asarray(colors, "<f4").reshape(-1, 3).tobytes())

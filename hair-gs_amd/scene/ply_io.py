@@ -106,8 +106,10 @@ def save_hair_ply(model, path):
                      ("ref_strand_root", table(ref, ["x", "y", "z"]))])
 
 
-def load_hair_ply(model, path):
-    els = read_ply(path)
+def load_hair_ply(model, path, elements=None, walk=True):
+    """elements: what read_ply(path) returned, if the caller has read the file already.  walk=False leaves strands_info unset, for a
+    caller that sets the strand roots itself before it walks (export_strands.py with a capture's roots)."""
+    els = read_ply(path) if elements is None else elements
     if len(els) != 5:
         raise ValueError(f"{path}: a strand model has 5 elements (vertex, edge, segment, strand_root_idx, ref_strand_root), got {len(els)}")
     vert, edge, seg, root, ref = (e[1] for e in els)
@@ -132,4 +134,5 @@ def load_hair_ply(model, path):
     model.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
     model.denom = torch.zeros((n, 1), device=dev)
     model._smooth_pairs = None
-    model.compute_strands_info()
+    if walk:
+        model.compute_strands_info()

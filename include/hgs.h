@@ -48,9 +48,10 @@ extern "C" {
  * 6, round 6: tile_delta in the image buffer; 7: every image-buffer field behind tile_cursor starts on a 256-byte boundary, and a
  * misaligned HgsHeadParams.tile_used is an error of hgs_loss_head_forward; 8: hgs_strand_grow_plan / hgs_strand_grow_fill;
  * 9: tile culling, the record form and the row sums are flag bits of each call instead of process-wide setters, and one render,
- * backward and size function each serves 3 and 7 channels; 10: hgs_pointcloud_normals / hgs_pointcloud_normals_scratch_bytes);
+ * backward and size function each serves 3 and 7 channels; 10: hgs_pointcloud_normals / hgs_pointcloud_normals_scratch_bytes;
+ * 11: one parameter-source struct for the forward, HgsParamForward; 12: hgs_strand_arclen / hgs_strand_resample);
  * the Python binding refuses a library whose version or struct sizes differ from its own */
-#define HGS_ABI_VERSION 11
+#define HGS_ABI_VERSION 12
 #define HGS_TILE 16 /* cuda_rasterizer/config.h:16-17 */
 
 int hgs_abi_version(void);
@@ -580,6 +581,28 @@ int hgs_strand_grow_fill(void* stream, int S, const long long* offsets, const lo
                          float growth_length, const float* length_src, const float* f_dc, const float* f_rest, int rest_floats,
                          const float* opacity, const float* mask, const float* width, long long* new_pairs, float* new_endpoints,
                          float* new_f_dc, float* new_f_rest, float* new_opacity, float* new_mask, float* new_width);
+
+/* hgs_strand_arclen / hgs_strand_resample (csrc/hgs_export.hip) <-> the strand-file export (scene/strand_export.py; the reference has
+ *   only scripts/convert_output.py's MeshLab PLYs of the joints): arc-length resampling of the strands of hgs_strand_walk_fill
+ *   (offsets[S+1], rows[total][2] root -> tip, seg_rows[total]: row of attr) to M points per strand with a per-segment attribute
+ *   table attr[P][C] (float32, 1 <= C <= 16).  Strand s, n segments on the vertices v_0..v_n: len_i = sqrt((dx*dx + dy*dy) + dz*dz),
+ *   cum_0 = 0, cum_{i+1} = cum_i + len_i, L = cum_n; joint attributes a_0 = attr[seg_0], a_n = attr[seg_{n-1}], a_i = 0.5 (attr[seg_{i-1}]
+ *   + attr[seg_i]); sample j: t = (j / (M - 1)) L, i = the largest index with cum_i <= t (at most n - 1), w = (t - cum_i) / len_i (0 if
+ *   len_i is 0), v_i + w (v_{i+1} - v_i) and a_i + w (a_{i+1} - a_i); samples 0 and M - 1 are (v_0, a_0) and (v_n, a_n) themselves.  All of
+ *   it float64 on the float32 inputs, operation by operation, rounded once to float32.
+ *   _arclen, one wavefront per strand: cum[offsets[s] + s + i] = cum_i (i = 0..n; the table has total + S entries and is the one place
+ *   _resample looks, so a strand may be any length) and length[s] = L, summed in segment order (the definition's bits); status[0]
+ *   (zeroed by the caller) becomes 1 if a row names an endpoint id outside [0, n_ep) -- that segment counts as length 0 -- and 2
+ *   if offsets does not describe `rows`.
+ *   _resample, one lane per output point, for the K strands kept[K] (int32, ascending): M >= 2 writes sample j of kept[k] to row
+ *   k M + j (n_out = K M); M == 0 writes the n + 1 joints with their joint attributes to rows out_offsets[k].. (out_offsets[K+1]: the
+ *   caller's prefix sums of n + 1, n_out = out_offsets[K]).  out_points [n_out][3], out_attrs [n_out][C], float32.  Rows of strands
+ *   or ids out of range are written as zeros.  No atomics: bitwise reproducible. */
+int hgs_strand_arclen(void* stream, int S, const long long* offsets, const long long* rows, long long total, const float* endpoints,
+                      int n_ep, double* cum, double* length, int* status);
+int hgs_strand_resample(void* stream, int S, const long long* offsets, const long long* rows, const long long* seg_rows, long long total,
+                        const float* endpoints, int n_ep, const float* attr, int P, int C, const double* cum, int K, const int* kept,
+                        int M, const long long* out_offsets, long long n_out, float* out_points, float* out_attrs);
 
 /* Strand metrics (csrc/hgs_metrics.hip) <-> pct_matched_points of the reference's loss/metrics.py:12-85: the cKDTree
  *   query_ball_point per (distance, angle) pair, the direction test and the per-point Python loop that counts matches and
