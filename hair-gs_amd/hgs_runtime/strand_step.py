@@ -72,7 +72,7 @@ class ViewTable:
                 m = m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
                 keep.append(m)
                 r.mask = m.data_ptr()
-                r.mask_count = float(m.sum().item())
+                r.mask_count = float(torch.count_nonzero(m).item())   # the kernels test `mask != 0` and count 1 (a {0, 255} mask)
             for k, v in enumerate(c.world_view_transform.detach().float().cpu().reshape(-1).tolist()):
                 r.viewmatrix[k] = v
             for k, v in enumerate(c.full_proj_transform.detach().float().cpu().reshape(-1).tolist()):

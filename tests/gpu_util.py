@@ -138,7 +138,7 @@ def run_loss_head(image, gt, aux, tile_used=None, fill=7.0):
         t.data_ptr() for t in (gt, aux["float_mask"], aux["orientation"], aux["confidence"], aux["mask"]))
     for k, v in enumerate(np.eye(4, dtype=np.float32).reshape(-1)):
         row.viewmatrix[k] = row.projmatrix[k] = float(v)
-    row.mask_count = float(aux["mask"].sum().item())
+    row.mask_count = float(torch.count_nonzero(aux["mask"]).item())
     targets = torch.from_numpy(np.frombuffer(bytes(row), dtype=np.uint8).copy()).to(dev)
     opt = OptimizationParams()
     hp = head_params(H, W, opt, 0, 0, 1e-6, True)
