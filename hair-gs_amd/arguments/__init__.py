@@ -73,6 +73,9 @@ class OptimizationParams(ParamGroup):
         # needs more is caught by the headroom check and the iterations since the last checkpoint are run again (exact, only time
         # is lost): raise it for captures whose views differ much in coverage
         ("capture_warmup_views", 2, False), ("capacity_slack", 2.0, False),
+        # the magnet term (lambda_magnet > 0) as a device op inside the fused, captured iteration (hgs_runtime.fused.magnet_loss)
+        # instead of the op-by-op single-pass iteration
+        ("fused_magnet", False, False),
     )
 
     def _finalise(self):

@@ -74,6 +74,10 @@ SIGNATURES = {
     "hgs_radius_pairs": (ci, [vp, ci, vp, vp, cf, cf, ci, ci, vp, vp, vp, ci]),
     "hgs_knn3": (ci, [vp, ci, vp, vp, vp]),
     "hgs_nearest_distance_f64": (ci, [vp, ci, ci, vp, vp, vp]),
+    "hgs_magnet_scratch_bytes": (sz, [ci, ci]),
+    "hgs_magnet_forward": (ci, [vp, ci, ci, vp, vp, vp, vp, cf, vp, sz, vp, vp, vp, vp, vp]),
+    "hgs_magnet_backward": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp, cf, vp, sz, vp]),
+    "hgs_set_magnet_search": (ci, [ci]),
     "hgs_pointcloud_normals_scratch_bytes": (sz, [ci, ci]),
     "hgs_pointcloud_normals": (ci, [vp, ci, ci, vp, vp, vp, vp, sz]),
     "hgs_strand_walk_ends": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp]),
@@ -200,7 +204,7 @@ HEAD_OUT = ["total", "l1", "dssim", "mask", "orientation", "smooth", "ori_count"
             "g_ori", "g_smooth", "total_fwd"]
 HEAD_NOUT = 16
 FUSED_PREPROCESS_MAX_TILES = 8192   # include/hgs.h HGS_FUSED_PREPROCESS_MAX_TILES
-ABI_VERSION = 12   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
+ABI_VERSION = 13   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
 
 
 def build(verbose=False):

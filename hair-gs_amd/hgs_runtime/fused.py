@@ -1,5 +1,5 @@
 """torch.autograd front-ends of the fused HIP kernels that replace PyTorch-side chains on the training-step path
-(include/hgs.h: hgs_strand_geometry_*, hgs_ssim_l1_*, hgs_orientation_loss_*).  GPU tensors only."""
+(include/hgs.h: hgs_strand_geometry_*, hgs_ssim_l1_*, hgs_orientation_loss_*, hgs_magnet_*).  GPU tensors only."""
 import ctypes as C
 import math
 
@@ -179,6 +179,103 @@ class _SmoothnessLoss(torch.autograd.Function):
 def smoothness_loss(endpoints, index_pairs, cos_th, eps):
     """Mean squared bending angle over the consecutive-segment pairs bent beyond the threshold (0 if none)."""
     return _SmoothnessLoss.apply(endpoints, index_pairs, cos_th, eps)
+
+
+class MagnetTable:
+    """What the magnet term's device op (include/hgs.h hgs_magnet_*) needs of the topology, built on the host side of a
+    topology event: `ends` (the degree-1 endpoint ids, ascending), `partner` (each end's segment partner), `mapping` (the
+    zero-initialised id -> partner table of loss/losses.py:137-138), all int32 on the model's device, and the op's scratch.
+    MagnetTable.of(model) remembers it on the model for as long as `endpoint_pairs` is the same tensor."""
+
+    def __init__(self, model):
+        pairs = model.endpoint_pairs
+        ep = model._endpoints
+        if not ep.is_cuda:
+            raise rt.HgsError("MagnetTable: the model must live on the GPU (libhgs.so has no CPU path)")
+        E = int(ep.shape[0])
+        if pairs.numel() == 0:          # (no segments: no ends; get_complementary_endpoint_idx needs a non-empty table)
+            ends = comp = torch.zeros(0, dtype=torch.long, device=ep.device)
+        else:
+            u, c = torch.unique(pairs, return_counts=True)
+            ends = u[c == 1]
+            comp, _ = model.get_complementary_endpoint_idx(ends)
+        mapping = torch.zeros(E, device=ep.device, dtype=torch.int32)
+        mapping[ends] = comp.to(torch.int32)
+        self.pairs, self.E, self.n = pairs, E, int(ends.shape[0])
+        self.ends, self.partner, self.mapping = ends.to(torch.int32).contiguous(), comp.to(torch.int32).contiguous(), mapping
+        self.scratch_bytes = int(rt.lib().hgs_magnet_scratch_bytes(self.n, E))
+        self.scratch = torch.empty((self.scratch_bytes + 256,), dtype=torch.uint8, device=ep.device)
+        self.scratch_ptr = (self.scratch.data_ptr() + 255) // 256 * 256
+
+    @classmethod
+    def of(cls, model):
+        cached = getattr(model, "_magnet_table_cache", None)
+        if cached is None or cached.pairs is not model.endpoint_pairs or cached.E != int(model._endpoints.shape[0]):
+            cached = model._magnet_table_cache = cls(model)
+        return cached
+
+
+class _MagnetLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, endpoints, table, min_val, info):
+        endpoints = rt.require_gpu_tensor(endpoints, "endpoints", torch.float32)
+        E, n, dev = int(endpoints.shape[0]), table.n, endpoints.device
+        if E != table.E:
+            raise rt.HgsError(f"magnet_loss: the table was built for {table.E} endpoints, the model has {E}: a topology event "
+                              "needs a new MagnetTable (FusedStrandStep.refresh())")
+        out = torch.empty((4,), dtype=torch.float32, device=dev)
+        ints = torch.empty((n, 5), dtype=torch.int32, device=dev).view(-1)        # sel [n,2] | nn_idx [n,3]
+        flts = torch.empty((n, 4), dtype=torch.float32, device=dev).view(-1)      # sq [n] | nn_d2 [n,3]
+        sel, nn_idx = ints[:2 * n], ints[2 * n:]
+        sq, nn_d2 = flts[:n], flts[n:]
+        with torch.cuda.device(dev):
+            rt.check(rt.lib().hgs_magnet_forward(rt.current_stream(), E, n, rt.ptr(endpoints), rt.ptr(table.ends),
+                                                 rt.ptr(table.partner), rt.ptr(table.mapping), float(min_val), table.scratch_ptr,
+                                                 table.scratch_bytes, rt.ptr(out), rt.ptr(sel), rt.ptr(sq), rt.ptr(nn_idx),
+                                                 rt.ptr(nn_d2)))
+        ctx.save_for_backward(endpoints, out, sel, sq)
+        ctx.table = table
+        if info is not None:
+            info.update(out=out, sel=sel.view(n, 2), sq=sq, nn_idx=nn_idx.view(n, 3), nn_d2=nn_d2.view(n, 3))
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        endpoints, out, sel, sq = ctx.saved_tensors
+        table = ctx.table
+        E, dev = int(endpoints.shape[0]), endpoints.device
+        g = g.contiguous().to(torch.float32)
+        d = torch.empty_like(endpoints)
+        with torch.cuda.device(dev):
+            rt.check(rt.lib().hgs_magnet_backward(rt.current_stream(), E, table.n, rt.ptr(endpoints), rt.ptr(table.ends), rt.ptr(sel),
+                                                  rt.ptr(sq), rt.ptr(out), rt.ptr(g), 1.0, table.scratch_ptr, table.scratch_bytes,
+                                                  rt.ptr(d)))
+        return d, None, None, None
+
+
+def magnet_loss(endpoints, table, min_val, info=None):
+    """strand_joints_magnet_loss (loss/losses.py) of `endpoints` under the topology of `table` (a MagnetTable) as one device op:
+    the scalar, differentiable w.r.t. endpoints.  `info`: a dict that receives the op's other outputs (device tensors, no copy):
+    "out" ([4]: the value; the rows of the mean and the valid ends as int32 bits in [1], [2] -- magnet_rows / magnet_valid read
+    them), "sel" ([n,2]: per position of the compacted list the selected position or -1, and the index into table.ends),
+    "sq" ([n]), "nn_idx" / "nn_d2" ([n,3]: the three nearest, what knn3_self gives on the valid ends)."""
+    return _MagnetLoss.apply(endpoints, table, min_val, info)
+
+
+def magnet_rows(info):
+    """Rows in the mean of the magnet_loss call that filled `info` (one read-back: tests and tools)."""
+    return int(info["out"].view(torch.int32)[1])
+
+
+def magnet_valid(info):
+    """Ends that survived the min_val test in the magnet_loss call that filled `info` (one read-back)."""
+    return int(info["out"].view(torch.int32)[2])
+
+
+def set_magnet_search(mode):
+    """The neighbour search of magnet_loss, process-wide: None / -1 automatic (by the number of ends), 0 tiles, 1 grid.  Returns
+    the previous mode.  A test and A/B switch: both paths give identical bits."""
+    return rt.lib().hgs_set_magnet_search(-1 if mode is None else int(mode))
 
 
 class FusedAdam(torch.optim.Optimizer):

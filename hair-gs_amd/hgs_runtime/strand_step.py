@@ -317,7 +317,8 @@ def _raster_head_forward(step, xyz, scale, quat, opacity, extra4, shs, endpoints
     if step.poison_unwritten and d_extra is not None:     # test aid, like dL/dimage in _head_raster_backward
         d_extra.fill_(float("nan"))
     # the tail of the head's reduction rides in the backward's parameter launch (include/hgs.h HgsHeadTail)
-    hp.defer_tail = 1 if (step.defer_tail and xyz.shape[0] > 0) else 0
+    # (with the magnet term loss() adds to the head's total right after this forward: the total must be complete by then)
+    hp.defer_tail = 1 if (step.defer_tail and xyz.shape[0] > 0 and getattr(step, "magnet", None) is None) else 0
     with torch.cuda.device(dev):
         rt.check(L.hgs_loss_head_forward(rt.current_stream(), C.byref(hp), planes[0:3].data_ptr(), planes[3].data_ptr(),
                                          planes[4:7].data_ptr(), vt.slot.data_ptr(), rt.ptr(endpoints), rt.ptr(smooth_idx),
@@ -581,15 +582,19 @@ class FusedStrandStep:
         # the backward's parameter launch instead of a launch of their own (GraphedStep, which always runs both, sets it)
         self.defer_tail = False
         self.last = {}
+        # the magnet term's topology table (hgs_runtime.fused.MagnetTable) when the term runs inside this iteration, else None
+        self.magnet = None
         self.refresh()
 
     def inline_adam_possible(self):
         """Can this iteration's backward apply the Adam update itself?  One rank, the parameters' backward fused into the
         rasterizer's (hgs_backward_multi_params; a strand model also needs the endpoint adjacency), a FusedAdam that holds
-        exactly the in-lane tensors (higher SH coefficients would need a launch of their own) -- and not switched off."""
+        exactly the in-lane tensors (higher SH coefficients would need a launch of their own) -- and not switched off.  Not with
+        the magnet term: the endpoints' gradient then has a second contributor (autograd adds the two), so the update cannot
+        run in the gather's lanes and Adam's own launch returns."""
         from hgs_runtime.fused import FusedAdam
         g = self.gaussians
-        return (self.fuse_param_backward and isinstance(getattr(g, "optimizer", None), FusedAdam)
+        return (self.magnet is None and self.fuse_param_backward and isinstance(getattr(g, "optimizer", None), FusedAdam)
                 and g._features_rest.numel() == 0 and getattr(self, "ep_segments", True) is not None
                 and bool(getattr(self.opt, "inline_adam", True)) and os.environ.get("HGS_INLINE_ADAM", "1") != "0"
                 and not (torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1))
@@ -620,6 +625,12 @@ class FusedStrandStep:
         self.smooth_pairs = rt.require_gpu_tensor(idx, "index_pairs", torch.int64) if n > 0 else None
         self.head = head_params(self.views.H, self.views.W, self.opt, n, g._endpoints.shape[0], g.min_val,
                                 self.views.has_float_mask)
+        # the magnet term inside the iteration (opt.fused_magnet): ends / partners of the topology as of now
+        self.lambda_magnet = float(getattr(self.opt, "lambda_magnet", 0.0))
+        self.magnet = None
+        if self.lambda_magnet > 0 and bool(getattr(self.opt, "fused_magnet", False)):
+            from hgs_runtime.fused import MagnetTable
+            self.magnet = MagnetTable.of(g)
         # endpoint adjacency for the gather-mode backward (HgsStrandFusion.ep_segments / ep_pairs): an endpoint of a
         # chain touches <= 2 segments and <= 4 smoothness-pair roles; anything denser keeps the scatter (atomic) mode.
         # Remembered on the model for as long as both index tables are the same tensors (a topology event assigns new ones): the
@@ -640,7 +651,17 @@ class FusedStrandStep:
     def loss(self):
         """(total loss, terms tensor) of the CURRENT slot view; differentiable w.r.t. the model parameters."""
         g = self.gaussians
-        return _StrandIteration.apply(g._endpoints, g._width, g._opacity, g._mask, g._features_dc, g._features_rest, self)
+        loss, terms = _StrandIteration.apply(g._endpoints, g._width, g._opacity, g._mask, g._features_dc, g._features_rest, self)
+        if self.magnet is not None:
+            # loss + lambda_magnet * term, exactly as loss_function_single_pass adds it: a second autograd node over the term's
+            # device op; autograd adds the two endpoint gradients.  A pass voided by a capacity overflow returns zero gradients
+            # from the node above but the magnet gradient stays in that step: the repeat of the step (eager, training_step) and
+            # the roll-back to the last checkpoint (captured, training()) discard such steps whole, so nothing is done here.
+            from hgs_runtime.fused import magnet_loss
+            m = magnet_loss(g._endpoints, self.magnet, g.min_val)
+            self.last["magnet"] = m.detach()
+            loss = loss + self.lambda_magnet * m
+        return loss, terms
 
     def backward(self, loss):
         """loss.backward() without the ones_like() launch."""
@@ -648,7 +669,10 @@ class FusedStrandStep:
 
     def terms(self):
         t = self.last["terms"]
-        return {k: t[i] for i, k in enumerate(rt.HEAD_OUT[1:6], start=1)}
+        d = {k: t[i] for i, k in enumerate(rt.HEAD_OUT[1:6], start=1)}
+        if "magnet" in self.last:
+            d["magnet"] = self.last["magnet"]
+        return d
 
     def update_densification_stats(self):
         """add_densification_stats + max_radii2D of the iteration just back-propagated (one launch)."""
@@ -738,6 +762,7 @@ class FusedCloudStep(FusedStrandStep):
     def refresh(self):
         g = self.gaussians
         self.smooth_pairs = None
+        self.magnet = None          # (a Gaussian cloud has no strand ends)
         self.head = head_params(self.views.H, self.views.W, self.opt, 0, 0, getattr(g, "min_val", 1e-7),
                                 self.views.has_float_mask)
 

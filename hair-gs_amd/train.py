@@ -195,9 +195,11 @@ class ViewSampler:
 
 def fused_step_applicable(gaussians, opt):
     """The fused iteration (hgs_runtime.strand_step) covers both models (Stage-I cloud, Stage-III strands) with the
-    single-pass rasterizer on the GPU and the reference's default loss terms (no magnet loss)."""
-    return (getattr(opt, "fused_step", True) and getattr(opt, "single_pass", True)
-            and gaussians.get_xyz.is_cuda and float(getattr(opt, "lambda_magnet", 0.0)) == 0.0)
+    single-pass rasterizer on the GPU and the reference's default loss terms; the magnet term (lambda_magnet > 0) only with
+    --fused_magnet, as a second autograd node over its device op (hgs_runtime.fused.magnet_loss) on a strand model."""
+    magnet = float(getattr(opt, "lambda_magnet", 0.0)) > 0.0
+    return bool(getattr(opt, "fused_step", True) and getattr(opt, "single_pass", True) and gaussians.get_xyz.is_cuda
+                and (not magnet or (bool(getattr(opt, "fused_magnet", False)) and isinstance(gaussians, HairGaussianModel))))
 
 
 class _EventInfo:
@@ -723,6 +725,10 @@ def training(gaussians, cameras, opt, iterations=None, extent=1.0, seed=0, log_e
             if vp.rank == 0:
                 print(f"training(): the fused iteration needs uniform views ({e}); running the op-by-op iteration eagerly")
             views, use_graph = None, False
+    if use_graph and views is None and float(getattr(opt, "lambda_magnet", 0.0)) > 0.0:
+        # the op-by-op magnet term selects its rows on the host (torch.unique, boolean masks): a capture refuses it.  Only its
+        # device op (--fused_magnet, a strand model) runs inside the captured step; otherwise every iteration is launched eagerly.
+        use_graph = False
     if views is not None:
         fused = fused_step_for(gaussians, views, opt, bg)   # eager launches of the same iteration (topology iterations)
         fused.defer_tail = bool(getattr(opt, "defer_head_tail", True))   # (training_step runs forward and backward together)

@@ -49,9 +49,9 @@ extern "C" {
  * misaligned HgsHeadParams.tile_used is an error of hgs_loss_head_forward; 8: hgs_strand_grow_plan / hgs_strand_grow_fill;
  * 9: tile culling, the record form and the row sums are flag bits of each call instead of process-wide setters, and one render,
  * backward and size function each serves 3 and 7 channels; 10: hgs_pointcloud_normals / hgs_pointcloud_normals_scratch_bytes;
- * 11: one parameter-source struct for the forward, HgsParamForward; 12: hgs_strand_arclen / hgs_strand_resample);
+ * 11: one parameter-source struct for the forward, HgsParamForward; 12: hgs_strand_arclen / hgs_strand_resample; 13: hgs_magnet_*);
  * the Python binding refuses a library whose version or struct sizes differ from its own */
-#define HGS_ABI_VERSION 12
+#define HGS_ABI_VERSION 13
 #define HGS_TILE 16 /* cuda_rasterizer/config.h:16-17 */
 
 int hgs_abi_version(void);
@@ -535,6 +535,45 @@ int hgs_radius_pairs(void* stream, int N, const float* pos, const float* dir, fl
  *   included (first, at distance 0); equal distances in ascending index order; fewer than 3 points: index -1, distance
  *   +inf.  Brute force through LDS tiles: the ends move every iteration and number in the thousands. */
 int hgs_knn3(void* stream, int N, const float* points, int* idx /* [N,3] */, float* dist2 /* [N,3] */);
+/* hgs_magnet_forward / hgs_magnet_backward <-> loss/losses.py strand_joints_magnet_loss (reference loss/losses.py:106-172) and its
+ *   autograd, statement for statement, as a device op (csrc/hgs_magnet.hip): no allocation, no host synchronisation, no copy to
+ *   the host; every launch on `stream`; launch shapes depend on n and E only, so a captured graph stays valid until the next
+ *   topology event.  Host side of a topology event (hgs_runtime.fused.MagnetTable):
+ *     ends[n]     int32, the degree-1 endpoint ids, ascending (torch.unique(endpoint_pairs, return_counts=True));
+ *     partner[n]  int32, each end's segment partner (get_complementary_endpoint_idx);
+ *     mapping[E]  int32, zero except mapping[ends[i]] = partner[i] (losses.py:137-138).
+ *   Device side, every call:
+ *     (a) ends whose own segment |endpoints[ends[i]] - endpoints[partner[i]]| is not longer than min_val are removed; every
+ *         neighbour index below is a POSITION in that compacted list (the rank is an exclusive scan on the device);
+ *     (b) the three nearest of every end, itself included, by (distance, position), distance = dx*dx + dy*dy + dz*dz in float32
+ *         without contraction: the indices and distances hgs_knn3 gives on the compacted points, bit for bit; fewer than three
+ *         comparable ends (or non-finite coordinates): index -1, distance +inf;
+ *     (c) the second is selected unless it equals the end's own position or the GLOBAL id of the end's partner, else the third;
+ *     (d) the selected position q, read as a global id, must have |endpoints[q] - endpoints[mapping[q]]| > min_val;
+ *     (e) rows with a missing neighbour or a non-finite distance are left out;
+ *     (f) out[0] = mean over the kept rows of the squared squared distance (the float32 products summed in float64 in a fixed
+ *         order); exactly 0 when no row is kept (fewer than three valid ends among the causes);
+ *     (g) d_endpoints = grad_out[0] * weight * 4 s (p - q) / m at the end, the opposite at its neighbour (s the squared distance,
+ *         m the kept rows), zero everywhere else; every endpoint is written.  No float atomics: the neighbour side is a key sort
+ *         of (selected position, own position) and a sum per destination in ascending order of the contributing end, so the bits
+ *         are the same from run to run and under either search path.
+ *   Outputs of the forward, all caller-owned, read back by the backward: out[4] (value; rows m and valid ends as int32 bits in
+ *   [1], [2]), sel[n,2] (position a: the selected position or -1 when the row is not kept; the index into `ends`, -1 behind the
+ *   valid ends), sq[n] (the kept rows' squared distance), nn_idx[n,3] / nn_d2[n,3] (statement (b), for tests).
+ *   scratch: >= hgs_magnet_scratch_bytes(n, E) bytes (every array is per end today: E is taken for the signature's sake and does
+ *   not enter the size), 256-byte aligned, private to one call at a time; the backward uses only what
+ *   it writes itself, so a forward on the same scratch may run between a forward and its backward.
+ * hgs_set_magnet_search: the search path of (b), process-wide: -1 automatic (by n), 0 tiles through LDS (brute force, candidate
+ *   range split over workgroups for small n), 1 grid of Morton cells (the plan of hgs_dist2).  Returns the previous mode.  Both
+ *   paths give identical bits in every output. */
+size_t hgs_magnet_scratch_bytes(int n_ends, int n_endpoints);
+int hgs_magnet_forward(void* stream, int E, int n, const float* endpoints, const int* ends, const int* partner, const int* mapping,
+                       float min_val, void* scratch, size_t scratch_bytes, float* out /* [4] */, int* sel /* [n,2] */,
+                       float* sq /* [n] */, int* nn_idx /* [n,3] */, float* nn_d2 /* [n,3] */);
+int hgs_magnet_backward(void* stream, int E, int n, const float* endpoints, const int* ends, const int* sel, const float* sq,
+                        const float* out, const float* grad_out /* device scalar */, float weight, void* scratch,
+                        size_t scratch_bytes, float* d_endpoints /* [E,3] */);
+int hgs_set_magnet_search(int mode);
 /* hgs_nearest_distance_f64 <-> scipy cKDTree(refs).query(points, k=1)[0] as compute_strands_info uses it on the strands' ends
  *   (scene/hair_gaussian_model.py:1466-1470): out[i] = min_m |points[i] - refs[m]| in float64 (points float32 [N,3], refs
  *   float64 [M,3], M >= 1). */
