@@ -99,7 +99,8 @@ def knn3_self(points):
     """(squared distances [n,3], indices [n,3]) of the 3 nearest points of `points` within the set itself, ascending, the
     point itself included -- what pytorch3d.ops.knn_points(p, p, K=3, return_sorted=True) returns for one cloud
     (reference loss/losses.py:139-144).  Indices only (no autograd): GPU tensors go through hgs_knn3, CPU tensors through
-    a chunked distance matrix.  Fewer than 3 points: index -1, distance +inf."""
+    a chunked distance matrix.  Fewer than 3 comparable candidates -- fewer than 3 points, or a non-finite coordinate in the point
+    or in the others: a squared distance of +inf or NaN is closer than nothing -- leave index -1, distance +inf, on both paths."""
     pts = points.detach().to(torch.float32).contiguous()
     n = pts.shape[0]
     if pts.is_cuda:
@@ -116,8 +117,13 @@ def knn3_self(points):
         diff = pts[s:s + 4096, None, :] - pts[None, :, :]
         dist = diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1] + diff[..., 2] * diff[..., 2]
         # ascending by (distance, index): a stable sort of the distances keeps equal ones in index order
+        # (a distance that is +inf or NaN -- a non-finite coordinate on either side -- compares closer to nothing, as in
+        # hgs_knn3: it sorts last as +inf and its slot keeps index -1)
+        dist = torch.where(dist < float("inf"), dist, torch.full_like(dist, float("inf")))
         order = torch.sort(dist, dim=1, stable=True)
-        d2[s:s + 4096, :k], idx[s:s + 4096, :k] = order.values[:, :k], order.indices[:, :k]
+        found = order.values[:, :k] < float("inf")
+        d2[s:s + 4096, :k] = order.values[:, :k]
+        idx[s:s + 4096, :k] = torch.where(found, order.indices[:, :k], torch.full_like(order.indices[:, :k], -1))
     return d2, idx
 
 

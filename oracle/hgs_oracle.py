@@ -18,7 +18,7 @@ _LIB = None
 
 def build(force=False):
     so = os.path.join(_HERE, "libhgs_oracle.so")
-    srcs = [os.path.join(_HERE, f) for f in ("raster_oracle.c", "knn_oracle.c", "strand_oracle.c", "Makefile")]
+    srcs = [os.path.join(_HERE, f) for f in ("raster_oracle.c", "knn_oracle.c", "strand_oracle.c", "knn_grid_port.c", "Makefile")]
     if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.check_call(["make", "-s", "-C", _HERE], stdout=subprocess.DEVNULL)
     return so
@@ -201,6 +201,20 @@ def dist2(points, want_debug=False):
     idx = np.zeros(P, np.uint32)
     lib().hgs_oracle_dist2(C.c_int(P), _p(p), _p(out), _p(codes), _p(idx))
     return (out, codes, idx) if want_debug else out
+
+
+GRID_NO_MARGIN, GRID_NO_OWN_GUARD, GRID_NO_CLAMP = 1, 2, 4
+
+
+def dist2_grid(points, flags=0):
+    """CPU port of distCUDA2's grid search (oracle/knn_grid_port.c) with single decisions switched off by `flags`:
+    (mean squared distances, lanes whose cube walk left the grid)."""
+    p = _arr(points, np.float32)
+    P = p.shape[0]
+    out = np.zeros(P, np.float32)
+    left = C.c_int64(0)
+    lib().hgs_oracle_dist2_grid(C.c_int(P), _p(p), _p(out), C.c_int(int(flags)), C.byref(left))
+    return out, int(left.value)
 
 
 def filter_strand_list_segments(strands_list):
