@@ -159,11 +159,12 @@ def _data_lines(path):
                 yield line
 
 
-def read_intrinsics_text(path):
+def read_intrinsics_text(path, pinhole_only=True):
+    """pinhole_only=False (undistort.py): every camera model is read, as read_intrinsics_binary does."""
     cams = {}
     for line in _data_lines(path):
         t = line.split()
-        if t[1] != "PINHOLE":   # the reference asserts this too: the rest of the pipeline assumes undistorted pinholes
+        if pinhole_only and t[1] != "PINHOLE":   # the reference asserts this too: the rest of the pipeline assumes undistorted pinholes
             raise AssertionError("only PINHOLE cameras are supported in text models")
         cams[int(t[0])] = Camera(id=int(t[0]), model=t[1], width=int(t[2]), height=int(t[3]),
                                  params=np.array([float(v) for v in t[4:]]))

@@ -87,6 +87,7 @@ SIGNATURES = {
                                   vp, vp]),
     "hgs_strand_arclen": (ci, [vp, ci, vp, vp, C.c_longlong, vp, ci, vp, vp, vp]),
     "hgs_strand_resample": (ci, [vp, ci, vp, vp, vp, C.c_longlong, vp, ci, vp, ci, ci, vp, ci, vp, ci, vp, C.c_longlong, vp, vp]),
+    "hgs_undistort_images": (ci, [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci]),
     "hgs_oriented_match_scratch_bytes": (sz, [ci]),
     "hgs_oriented_match": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, sz]),
     "hgs_strand_votes": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]),
@@ -204,7 +205,7 @@ HEAD_OUT = ["total", "l1", "dssim", "mask", "orientation", "smooth", "ori_count"
             "g_ori", "g_smooth", "total_fwd"]
 HEAD_NOUT = 16
 FUSED_PREPROCESS_MAX_TILES = 8192   # include/hgs.h HGS_FUSED_PREPROCESS_MAX_TILES
-ABI_VERSION = 13   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
+ABI_VERSION = 14   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
 
 
 def build(verbose=False):

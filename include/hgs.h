@@ -49,9 +49,10 @@ extern "C" {
  * misaligned HgsHeadParams.tile_used is an error of hgs_loss_head_forward; 8: hgs_strand_grow_plan / hgs_strand_grow_fill;
  * 9: tile culling, the record form and the row sums are flag bits of each call instead of process-wide setters, and one render,
  * backward and size function each serves 3 and 7 channels; 10: hgs_pointcloud_normals / hgs_pointcloud_normals_scratch_bytes;
- * 11: one parameter-source struct for the forward, HgsParamForward; 12: hgs_strand_arclen / hgs_strand_resample; 13: hgs_magnet_*);
+ * 11: one parameter-source struct for the forward, HgsParamForward; 12: hgs_strand_arclen / hgs_strand_resample; 13: hgs_magnet_*;
+ * 14: hgs_undistort_images);
  * the Python binding refuses a library whose version or struct sizes differ from its own */
-#define HGS_ABI_VERSION 13
+#define HGS_ABI_VERSION 14
 #define HGS_TILE 16 /* cuda_rasterizer/config.h:16-17 */
 
 int hgs_abi_version(void);
@@ -642,6 +643,20 @@ int hgs_strand_arclen(void* stream, int S, const long long* offsets, const long 
 int hgs_strand_resample(void* stream, int S, const long long* offsets, const long long* rows, const long long* seg_rows, long long total,
                         const float* endpoints, int n_ep, const float* attr, int P, int C, const double* cum, int K, const int* kept,
                         int M, const long long* out_offsets, long long n_out, float* out_points, float* out_attrs);
+
+/* hgs_undistort_images (csrc/hgs_undistort.hip) <-> the undistortion of a COLMAP capture (utils/undistort.py, undistort.py; the reference
+ *   leaves it to COLMAP's image_undistorter): N images [N][Hs][Ws][C] uint8 (C = 1, 3 or 4, PIL's layout) seen through the camera
+ *   `model` (COLMAP's model id: SIMPLE_PINHOLE 0, PINHOLE 1, SIMPLE_RADIAL 2, RADIAL 3, OPENCV 4, FULL_OPENCV 6; any other is an error)
+ *   with COLMAP's parameter list src_params_host[12] (host; the model's leading entries are read) are resampled into the pinhole camera
+ *   dst_pinhole_host[4] = (fx, fy, cx, cy) (host) of Wd x Hd pixels: dst [N][Hd][Wd][C].  Output pixel (x, y): u = ((x + 0.5) - cx') / fx',
+ *   v = ((y + 0.5) - cy') / fy', (sx, sy) = img_from_cam(u, v) - 0.5 in float64, every operation rounded once in the order utils/undistort.py
+ *   states; the sample is valid iff 0 <= sx <= Ws - 1 and 0 <= sy <= Hs - 1; x0 = floor(sx), x1 = min(x0 + 1, Ws - 1), wx = sx - x0 (likewise
+ *   y), value = (1 - wy)*((1 - wx)*p00 + wx*p01) + wy*((1 - wx)*p10 + wx*p11).  mode 0 (bilinear): floor(value + 0.5); mode 1 (threshold,
+ *   for masks): 255 where value >= 127.5, else 0; an invalid sample gives 0.  valid (nullable): [Hd][Wd], 1 where the sample is valid.
+ *   Bad arguments (N <= 0, sizes <= 0, another C, model or mode, a null buffer, an image above 2^31 - 1 bytes) return non-zero
+ *   before anything is launched. */
+int hgs_undistort_images(void* stream, int N, int C, int Hs, int Ws, int Hd, int Wd, int model, const double* src_params_host,
+                         const double* dst_pinhole_host, const unsigned char* src, unsigned char* dst, unsigned char* valid, int mode);
 
 /* Strand metrics (csrc/hgs_metrics.hip) <-> pct_matched_points of the reference's loss/metrics.py:12-85: the cKDTree
  *   query_ball_point per (distance, angle) pair, the direction test and the per-point Python loop that counts matches and
