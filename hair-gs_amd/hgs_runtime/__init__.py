@@ -88,6 +88,10 @@ SIGNATURES = {
     "hgs_strand_arclen": (ci, [vp, ci, vp, vp, C.c_longlong, vp, ci, vp, vp, vp]),
     "hgs_strand_resample": (ci, [vp, ci, vp, vp, vp, C.c_longlong, vp, ci, vp, ci, ci, vp, ci, vp, ci, vp, C.c_longlong, vp, vp]),
     "hgs_undistort_images": (ci, [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci]),
+    "hgs_carve_view_bytes": (sz, []),
+    "hgs_carve_votes": (ci, [vp, C.c_longlong, vp, ci, vp, vp, vp, vp, vp, vp]),
+    "hgs_carve_grid": (ci, [vp, vp, C.c_double, ci, ci, ci, ci, vp, vp, ci, ci, vp]),
+    "hgs_carve_shell": (ci, [vp, ci, ci, ci, vp, vp]),
     "hgs_oriented_match_scratch_bytes": (sz, [ci]),
     "hgs_oriented_match": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, sz]),
     "hgs_strand_votes": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]),
@@ -170,6 +174,12 @@ class RasterModel(C.Structure):
                 ("ka", C.c_double), ("kd", C.c_double)]
 
 
+class CarveView(C.Structure):
+    """include/hgs.h HgsCarveView (152 bytes; an array of them lives in device memory: built by utils/carve.py, uploaded as bytes)."""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("W", C.c_int32), ("H", C.c_int32), ("mask_offset", C.c_int64), ("image_offset", C.c_int64)]
+
+
 class AdamInline(C.Structure):
     """include/hgs.h HgsAdamInline."""
     _fields_ = [("slot", AdamSlot * 6), ("beta1", cf), ("beta2", cf), ("eps", cf)]
@@ -205,7 +215,7 @@ HEAD_OUT = ["total", "l1", "dssim", "mask", "orientation", "smooth", "ori_count"
             "g_ori", "g_smooth", "total_fwd"]
 HEAD_NOUT = 16
 FUSED_PREPROCESS_MAX_TILES = 8192   # include/hgs.h HGS_FUSED_PREPROCESS_MAX_TILES
-ABI_VERSION = 14   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
+ABI_VERSION = 15   # include/hgs.h HGS_ABI_VERSION: bumped whenever a struct, a signature or a buffer layout changes
 
 
 def build(verbose=False):
@@ -239,7 +249,7 @@ def lib():
                        ("hgs_strand_fusion_bytes", StrandFusion), ("hgs_param_forward_bytes", ParamForward),
                        ("hgs_param_backward_bytes", ParamBackward),
                        ("hgs_adam_prep_bytes", AdamPrep), ("hgs_adam_inline_bytes", AdamInline),
-                       ("hgs_raster_model_bytes", RasterModel)):
+                       ("hgs_raster_model_bytes", RasterModel), ("hgs_carve_view_bytes", CarveView)):
             if getattr(L, fn)() != C.sizeof(st):
                 raise HgsError(f"{LIB_PATH}: {fn}() = {getattr(L, fn)()} but the binding's struct has {C.sizeof(st)} bytes: "
                                "rebuild with hgs_runtime.build()")
@@ -271,6 +281,44 @@ def require_gpu_tensor(t, name, dtype=None):
     if dtype is not None and t.dtype != dtype:
         raise HgsError(f"{name} must be {dtype}, got {t.dtype}")
     return t.contiguous()
+
+
+def require_device_buffer(t, name, dtype):
+    """A contiguous device tensor of `dtype`, as it is: nothing is copied or converted on the way to a kernel."""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise HgsError(f"{name} must be a CUDA(HIP) tensor: libhgs.so only runs on the GPU, there is no CPU path")
+    if t.dtype != dtype:
+        raise HgsError(f"{name} must be {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise HgsError(f"{name} must be contiguous")
+    return t
+
+
+def carve_check(records, views_dev, masks, images=None):
+    """What hgs_carve_* may not be called without (include/hgs.h): `records`, the host copy (a CarveView array) of the view records in
+    views_dev, name a mask -- and, where image_offset >= 0, an image -- that lies inside its buffer; every buffer is a contiguous
+    uint8 device tensor.  Returns the number of views."""
+    import torch
+    V = len(records)
+    if not 1 <= V <= 4096:
+        raise HgsError(f"{V} views (1 to 4096)")
+    require_device_buffer(views_dev, "views", torch.uint8)
+    require_device_buffer(masks, "masks", torch.uint8)
+    if images is not None:
+        require_device_buffer(images, "images", torch.uint8)
+    if views_dev.numel() != V * C.sizeof(CarveView):
+        raise HgsError(f"the view buffer holds {views_dev.numel()} bytes, {V} views take {V * C.sizeof(CarveView)}")
+    for k in range(V):
+        r = records[k]
+        if r.W < 1 or r.H < 1:
+            raise HgsError(f"view {k}: {r.W} x {r.H} pixels")
+        if r.mask_offset < 0 or r.mask_offset + r.W * r.H > masks.numel():
+            raise HgsError(f"view {k}: its mask (offset {r.mask_offset}, {r.W} x {r.H}) does not lie inside the mask buffer of "
+                           f"{masks.numel()} bytes")
+        if r.image_offset >= 0 and (images is None or r.image_offset + 3 * r.W * r.H > images.numel()):
+            raise HgsError(f"view {k}: its image (offset {r.image_offset}, {r.W} x {r.H} x 3) does not lie inside the image buffer")
+    return V
 
 
 KERNEL_COUNT = 18

@@ -50,9 +50,9 @@ extern "C" {
  * 9: tile culling, the record form and the row sums are flag bits of each call instead of process-wide setters, and one render,
  * backward and size function each serves 3 and 7 channels; 10: hgs_pointcloud_normals / hgs_pointcloud_normals_scratch_bytes;
  * 11: one parameter-source struct for the forward, HgsParamForward; 12: hgs_strand_arclen / hgs_strand_resample; 13: hgs_magnet_*;
- * 14: hgs_undistort_images);
+ * 14: hgs_undistort_images; 15: hgs_carve_votes / hgs_carve_grid / hgs_carve_shell and HgsCarveView);
  * the Python binding refuses a library whose version or struct sizes differ from its own */
-#define HGS_ABI_VERSION 14
+#define HGS_ABI_VERSION 15
 #define HGS_TILE 16 /* cuda_rasterizer/config.h:16-17 */
 
 int hgs_abi_version(void);
@@ -657,6 +657,33 @@ int hgs_strand_resample(void* stream, int S, const long long* offsets, const lon
  *   before anything is launched. */
 int hgs_undistort_images(void* stream, int N, int C, int Hs, int Ws, int Hd, int Wd, int model, const double* src_params_host,
                          const double* dst_pinhole_host, const unsigned char* src, unsigned char* dst, unsigned char* valid, int mode);
+
+/* hgs_carve_votes / hgs_carve_grid / hgs_carve_shell (csrc/hgs_carve.hip) <-> the Stage-I point cloud carved from a capture's hair masks
+ *   (utils/carve.py states the contract, init_cloud.py is the driver; the reference starts from COLMAP's points or the FLAME vertices).
+ *   A view is a PINHOLE camera with its image's pose: R[9] row-major world -> camera, t[3], fx, fy, cx, cy (COLMAP's principal point),
+ *   W, H, and the byte offsets of its uint8 mask [H][W] and RGB image [H][W][3] in ONE mask buffer and ONE image buffer
+ *   (image_offset = -1: none).  Vote of the point (x, y, z) in view k, float64, one rounding per operation in this order:
+ *     xc = ((R00*x + R01*y) + R02*z) + tx (yc, zc: rows 1, 2);  u = fx*(xc/zc) + cx, v = fy*(yc/zc) + cy;
+ *     seen iff zc > 0 and 0 <= u < W and 0 <= v < H (a NaN: not seen);  px = floor(u), py = floor(v);  hit iff seen and mask[py][px] != 0.
+ *   _votes: seen[N], hits[N] = the counts over the V views, rgb_sum[N][3] (nullable; needs images) = the sum of image[py][px] over the
+ *   views that hit and have an image.  No early exit: the counts are the contract.  N == 0 launches nothing.
+ *   _grid: occ[nz][ny][nx] = 1 where the voxel centre origin_host[k] + (i_k + 0.5)*h is kept: seen >= min_views and 100*hits >=
+ *   min_percent*seen (integers, min_views >= 1, 0 <= min_percent <= 100).  A voxel's view loop stops once the rule is decided; the
+ *   result is that of the full counts.  1 <= nx, ny, nz <= 1024 and 1 <= V <= 4096, anything else is an error before any launch.
+ *   _shell: out = 1 where occ != 0 and one of the six face neighbours is 0 or outside the grid.
+ *   The kernels trust the offsets: the caller (hgs_runtime.carve_check) guarantees mask_offset + W*H and image_offset + 3*W*H lie inside
+ *   their buffers; `seen` guarantees 0 <= px < W and 0 <= py < H.  views_dev: V records in device memory. */
+typedef struct HgsCarveView {
+  double R[9], t[3], fx, fy, cx, cy;
+  int32_t W, H;
+  int64_t mask_offset, image_offset;
+} HgsCarveView;
+size_t hgs_carve_view_bytes(void);
+int hgs_carve_votes(void* stream, long long N, const double* points, int V, const HgsCarveView* views_dev, const unsigned char* masks,
+                    const unsigned char* images, int* seen, int* hits, int* rgb_sum);
+int hgs_carve_grid(void* stream, const double* origin_host, double h, int nx, int ny, int nz, int V, const HgsCarveView* views_dev,
+                   const unsigned char* masks, int min_views, int min_percent, unsigned char* occ);
+int hgs_carve_shell(void* stream, int nx, int ny, int nz, const unsigned char* occ, unsigned char* out);
 
 /* Strand metrics (csrc/hgs_metrics.hip) <-> pct_matched_points of the reference's loss/metrics.py:12-85: the cKDTree
  *   query_ball_point per (distance, angle) pair, the direction test and the per-point Python loop that counts matches and
