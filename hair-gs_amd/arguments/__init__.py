@@ -43,7 +43,8 @@ class ParamGroup:
 class ModelParams(ParamGroup):
     NAME = "Loading Parameters"
     FIELDS = (("source_path", "", True), ("model_path", "", True), ("images", "images", True), ("sh_degree", 0, False),
-              ("resolution", -1, True), ("data_device", "cuda", False), ("eval", False, False))
+              ("resolution", -1, True), ("data_device", "cuda", False), ("eval", False, False),
+              ("init_directions", False, False), ("direction_stretch", 3.0, False))
 
     def __init__(self, parser=None, sentinel=False):
         super().__init__(parser, sentinel)

@@ -90,12 +90,15 @@ def fetchPly(path):
                            normals=np.stack([v["nx"], v["ny"], v["nz"]], axis=1))
 
 
-def storePly(path, xyz, rgb):
+def storePly(path, xyz, rgb, normals=None):
+    """normals (optional, [n, 3]): the nx, ny, nz columns, zeros without (init_cloud.py --directions writes hair directions there)."""
     n = xyz.shape[0]
     arr = np.zeros(n, dtype=[("x", "f4"), ("y", "f4"), ("z", "f4"), ("nx", "f4"), ("ny", "f4"), ("nz", "f4"),
                              ("red", "u1"), ("green", "u1"), ("blue", "u1")])
     arr["x"], arr["y"], arr["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
     arr["red"], arr["green"], arr["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    if normals is not None:
+        arr["nx"], arr["ny"], arr["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     write_ply(path, [("vertex", arr)])
 
 

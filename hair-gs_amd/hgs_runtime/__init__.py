@@ -92,6 +92,8 @@ SIGNATURES = {
     "hgs_carve_votes": (ci, [vp, C.c_longlong, vp, ci, vp, vp, vp, vp, vp, vp]),
     "hgs_carve_grid": (ci, [vp, vp, C.c_double, ci, ci, ci, ci, vp, vp, ci, ci, vp]),
     "hgs_carve_shell": (ci, [vp, ci, ci, ci, vp, vp]),
+    "hgs_lift_moments": (ci, [vp, C.c_longlong, vp, ci, vp, vp, vp, vp, vp, vp, C.c_double, ci, vp, vp, vp]),
+    "hgs_lift_solve": (ci, [vp, C.c_longlong, vp, vp, ci, vp, vp]),
     "hgs_oriented_match_scratch_bytes": (sz, [ci]),
     "hgs_oriented_match": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, sz]),
     "hgs_strand_votes": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]),
@@ -318,6 +320,25 @@ def carve_check(records, views_dev, masks, images=None):
                            f"{masks.numel()} bytes")
         if r.image_offset >= 0 and (images is None or r.image_offset + 3 * r.W * r.H > images.numel()):
             raise HgsError(f"view {k}: its image (offset {r.image_offset}, {r.W} x {r.H} x 3) does not lie inside the image buffer")
+    return V
+
+
+def lift_check(records, views_dev, masks, orients, confs, tab, images=None):
+    """What hgs_lift_moments may not be called without (include/hgs.h): carve_check's guarantee for the masks, extended to the
+    orientation and confidence buffers (addressed by the same mask_offset), and a float64 table of 256 x 2 entries.  `images`: the
+    image buffer of records that name one (the lift does not read it).  Returns the number of views."""
+    import torch
+    V = carve_check(records, views_dev, masks, images)
+    for name, buf in (("orients", orients), ("confs", confs)):
+        require_device_buffer(buf, name, torch.uint8)
+        for k in range(V):
+            r = records[k]
+            if r.mask_offset + r.W * r.H > buf.numel():
+                raise HgsError(f"view {k}: its plane (offset {r.mask_offset}, {r.W} x {r.H}) does not lie inside the {name} buffer of "
+                               f"{buf.numel()} bytes")
+    require_device_buffer(tab, "tab", torch.float64)
+    if tab.numel() != 512:
+        raise HgsError(f"the sine / cosine table holds {tab.numel()} values, 256 x 2 expected")
     return V
 
 

@@ -4,6 +4,7 @@ cloud is sparse where hair is and dense on the face, the shoulders and the backg
   python init_cloud.py -s <scene> [--mode hull|filter|both] [--grid 256] [--bounds x0 y0 z0 x1 y1 z1]
                        [--min_views 3] [--min_percent 50] [--dilate 0] [--no_shell] [--max_points 200000]
                        [--images images] [--device cuda|cpu] [--overwrite]
+                       [--directions [--orientations orientations] [--rounds 3] [--sigma_deg 10] [--min_conf 1] [--min_coherence 0]]
 Reads <scene>/sparse/0 (binary or text; PINHOLE and SIMPLE_PINHOLE cameras only -- undistort.py makes them), <scene>/masks/<name> for
 every image of the model and, for the hull's colours, <scene>/<images>/<name>.
   hull    a --grid voxel grid over the automatic bounds (utils.carve.auto_bounds) or over --bounds is tested against every mask; a voxel
@@ -19,7 +20,13 @@ The write is in place and loses nothing: on the first run sparse/0/points3D.bin 
 a scene without points gets an empty points3D.colmap.bin -- and later runs read the COLMAP points from that backup and refuse to
 replace their predecessor's result without --overwrite.  The new points3D.bin is written under a temporary name and renamed into
 place; the loader's points3D.ply conversion of the old points is removed.  The points get ids 1..n and empty tracks: the point ids
-that images.bin refers to become stale, and nothing in this project reads them.  main() returns the number of points written."""
+that images.bin refers to become stale, and nothing in this project reads them.  main() returns the number of points written.
+--directions also lifts a 3-D hair direction for every written point from the views' orientation maps (utils/lift.py states the
+arithmetic): <scene>/<orientations>/<stem>_orientation.png and _confidence.png of every view are read (orient.py writes them), the
+views that have the point in frame, on the (dilated) mask and with a confidence of at least --min_conf vote in --rounds re-weighted
+rounds of scale --sigma_deg, and sparse/0/points3D.ply is written with the same points and colours and the direction in nx, ny, nz --
+zero where fewer than two views determine it or its coherence is below --min_coherence.  The loader reads that file as it is, and
+training with --init_directions starts from Gaussians stretched along it.  Without the flag no points3D.ply is written."""
 import os
 import sys
 
@@ -59,6 +66,23 @@ def _read_plane(path, view, what, mode):
     if a.shape[:2] != (view.H, view.W):
         _fail(f"{path}: {what} of {a.shape[1]} x {a.shape[0]} pixels, its camera has {view.W} x {view.H}")
     return np.array(a)                                       # (a writable copy: PIL hands out a read-only view)
+
+
+def _stem(view):
+    return os.path.basename(view.name).split(".")[0]             # (the loader's rule, data/dataset_readers.py)
+
+
+def lift_normals(voter, orients, confs, xyz, args):
+    """(normals f64 [n, 3], coherence f64 [n]) of the written points: utils.lift's directions, zero below --min_coherence."""
+    from utils import lift
+    if voter.device is None:
+        d, coherence, _ = lift.lift_directions(xyz, voter.views, voter.masks, orients, confs, args.rounds, args.sigma_deg, args.min_conf)
+    else:
+        import torch
+        packed = lift.pack(voter.views, voter.masks, orients, confs, voter.device, carve_packed=voter.packed)
+        pts = torch.from_numpy(np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)).to(voter.device)
+        d, coherence, _ = (t.cpu().numpy() for t in lift.directions_device(pts, packed, args.rounds, args.sigma_deg, args.min_conf))
+    return np.where((coherence >= args.min_coherence)[:, None], d, 0.0), coherence
 
 
 class _Voter:
@@ -148,6 +172,12 @@ def main(argv=None):
     parser.add_argument("--images", "-i", default="images")
     parser.add_argument("--device", default="cuda", help="cuda: the HIP kernels; cpu: the numpy path")
     parser.add_argument("--overwrite", action="store_true")
+    parser.add_argument("--directions", action="store_true", help="also lift hair directions into sparse/0/points3D.ply's normals")
+    parser.add_argument("--orientations", default="orientations", help="folder of the <stem>_orientation.png / _confidence.png maps")
+    parser.add_argument("--rounds", type=int, default=3, help="re-weighted rounds after the plain least-squares one")
+    parser.add_argument("--sigma_deg", type=float, default=10.0, help="angular scale of the re-weighting")
+    parser.add_argument("--min_conf", type=int, default=1, help="smallest confidence byte (0 to 255) that votes")
+    parser.add_argument("--min_coherence", type=float, default=0.0, help="directions below this coherence are written as zero")
     args = parser.parse_args(argv)
     from data.colmap import read_points3D_binary, read_points3D_text, write_points3D_arrays
     from undistort import read_sparse
@@ -156,6 +186,8 @@ def main(argv=None):
         _fail(f"--device {args.device}: cuda or cpu")
     if args.min_views < 1 or not 0 <= args.min_percent <= 100 or args.dilate < 0 or args.max_points < 1 or not 1 <= args.grid <= carve.MAX_DIM:
         _fail(f"--min_views >= 1, 0 <= --min_percent <= 100, --dilate >= 0, --max_points >= 1 and 1 <= --grid <= {carve.MAX_DIM} expected")
+    if args.directions and (args.rounds < 0 or not 0 <= args.min_conf <= 255 or not 0.0 < args.sigma_deg < 180.0):
+        _fail("--rounds >= 0, 0 <= --min_conf <= 255 and 0 < --sigma_deg < 180 expected")
     src = args.source_path
     sparse = os.path.join(src, "sparse", "0")
     if not os.path.isdir(os.path.join(src, "masks")):
@@ -178,6 +210,11 @@ def main(argv=None):
     need_images = args.mode in ("hull", "both")
     masks = [_read_plane(os.path.join(src, "masks", os.path.basename(v.name)), v, "the mask", "L") for v in views]
     imgs = [_read_plane(os.path.join(src, args.images, os.path.basename(v.name)), v, "the image", "RGB") for v in views] if need_images else None
+    orients = confs = None
+    if args.directions:
+        folder = os.path.join(src, args.orientations)
+        orients = [_read_plane(os.path.join(folder, f"{_stem(v)}_orientation.png"), v, "the orientation map", "L") for v in views]
+        confs = [_read_plane(os.path.join(folder, f"{_stem(v)}_confidence.png"), v, "the confidence map", "L") for v in views]
     voter = _Voter(views, masks, imgs, None if args.device == "cpu" else "cuda", args.dilate)
     parts = []
     if args.mode in ("filter", "both"):
@@ -201,10 +238,19 @@ def main(argv=None):
         else:
             write_points3D_arrays(np.zeros((0, 3)), np.zeros((0, 3), np.uint8), np.zeros(0), os.path.join(sparse, BACKUPS[0]))
     os.replace(tmp, result)
-    stale = os.path.join(sparse, "points3D.ply")             # (the loader's conversion of the old points)
-    if os.path.exists(stale):
-        os.remove(stale)
+    ply = os.path.join(sparse, "points3D.ply")               # (the loader's conversion of the old points)
+    if os.path.exists(ply):
+        os.remove(ply)
     print(f"{n} point(s) written to {result}")
+    if args.directions:
+        from data.dataset_readers import storePly
+        normals, coherence = lift_normals(voter, orients, confs, xyz, args)
+        has = (normals != 0.0).any(axis=1)
+        tmp = f"{ply}.{os.getpid()}.tmp"                         # (under a private name and renamed, as the loader writes it)
+        storePly(tmp, xyz, rgb, normals)
+        os.replace(tmp, ply)
+        print(f"directions: {int(has.sum())} of {n} point(s) got one, median coherence "
+              f"{float(np.median(coherence[has])) if has.any() else 0.0:.3f}; written to {ply}")
     return n
 
 

@@ -19,6 +19,26 @@ def _covariance_from_scaling_rotation(scaling, scaling_modifier, rotation):
     return strip_symmetric(L @ L.transpose(1, 2))
 
 
+def direction_init(dist2, normals, stretch):
+    """(scales_log [n, 3], rots [n, 4]) of Gaussians elongated along a per-point line (utils/lift.py's directions, read from the
+    cloud's normals).  A row with a non-zero normal: d = normal/|normal|, negated when d_x < 0 (a line has no sign, and this keeps the
+    quaternion away from its singular case d = -e_x); q = normalise(1 + d_x, 0, -d_z, d_y), the rotation that takes the local x axis
+    to d; scale_x = log(stretch*sqrt(dist2)), scale_y and scale_z = log(sqrt(dist2)).  A row with a zero normal: the identity
+    quaternion and the isotropic scale, exactly create_from_pcd's values without directions."""
+    scales = torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3)
+    rots = torch.zeros((dist2.shape[0], 4), device=dist2.device)
+    rots[:, 0] = 1
+    normals = normals.to(dist2.device, torch.float32)
+    length = torch.sqrt((normals * normals).sum(dim=1))
+    has = (length > 0) & torch.isfinite(length)
+    d = normals[has] / length[has, None]
+    d = torch.where(d[:, 0:1] < 0, -d, d)
+    q = torch.stack([1 + d[:, 0], torch.zeros_like(d[:, 0]), -d[:, 2], d[:, 1]], dim=1)
+    rots[has] = q / torch.sqrt((q * q).sum(dim=1, keepdim=True))
+    scales[has, 0] = torch.log(stretch * torch.sqrt(dist2[has]))
+    return scales, rots
+
+
 class GaussianModel:
     min_val = 1e-7
     dist_to_scale_factor = 0.5102133812190369  # 1 / Phi^-1(1 - pval/2) at pval = 0.05 (reference :35)
@@ -133,7 +153,9 @@ class GaussianModel:
         from scene.ply_io import load_gaussian_ply
         load_gaussian_ply(self, path)
 
-    def create_from_pcd(self, pcd: BasicPointCloud):
+    def create_from_pcd(self, pcd: BasicPointCloud, init_directions=False, direction_stretch=3.0):
+        """init_directions: the cloud's normals are hair directions (init_cloud.py --directions): a point that has one starts as a
+        Gaussian stretched direction_stretch times along it (direction_init); the stretch is a knob, not a measurement."""
         dev = self.device
         pts = torch.tensor(np.asarray(pcd.points)).float().to(dev)
         n = pts.shape[0]
@@ -145,6 +167,8 @@ class GaussianModel:
         scales = torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3)
         rots = torch.zeros((n, 4), device=dev)
         rots[:, 0] = 1
+        if init_directions:
+            scales, rots = direction_init(dist2, torch.tensor(np.asarray(pcd.normals)).float(), float(direction_stretch))
         opacities = inverse_sigmoid(0.1 * torch.ones((n, 1), dtype=torch.float, device=dev))
         masks = inverse_sigmoid(0.5 * torch.ones((n, 1), dtype=torch.float, device=dev))
         self._xyz = nn.Parameter(pts.requires_grad_(True))

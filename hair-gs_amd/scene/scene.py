@@ -112,7 +112,8 @@ class Scene:
                         for s in resolution_scales}
         if self.loaded_iter is None:
             self.gaussians = GaussianModel(args.sh_degree, self.cameras_extent, device=dev)
-            self.gaussians.create_from_pcd(info.point_cloud)
+            self.gaussians.create_from_pcd(info.point_cloud, init_directions=getattr(args, "init_directions", False),
+                                           direction_stretch=getattr(args, "direction_stretch", 3.0))
             self.loaded_iter = 0
         else:
             path = os.path.join(pc_dir, f"iteration_{self.loaded_iter}", "point_cloud.ply")

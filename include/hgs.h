@@ -685,6 +685,28 @@ int hgs_carve_grid(void* stream, const double* origin_host, double h, int nx, in
                    const unsigned char* masks, int min_views, int min_percent, unsigned char* occ);
 int hgs_carve_shell(void* stream, int nx, int ny, int nz, const unsigned char* occ, unsigned char* out);
 
+/* hgs_lift_moments / hgs_lift_solve (csrc/hgs_lift.hip) <-> 3-D hair directions lifted from the capture's 2-D orientation maps for the
+ *   Stage-I cloud (utils/lift.py states the contract, init_cloud.py --directions is the driver; the reference starts from isotropic
+ *   Gaussians).  The views are HgsCarveView records; orients and confs are uint8 planes laid out like masks, at the records' mask_offset
+ *   of their own buffers.  tab_dev[256][2] = (sin, cos)(o*pi/255), float64, built on the host.  Term of the point (x, y, z) in view k,
+ *   float64, one rounding per operation in this order, with xc, yc, zc, u, v, seen, px, py as in hgs_carve_votes:
+ *     used iff seen and mask[py][px] != 0 and conf[py][px] >= min_conf;  o = orient[py][px];  a = tab[o][0]/fx, b = tab[o][1]/fy;
+ *     ncx = -(zc*b), ncy = zc*a, ncz = xc*b - yc*a;  n_i = (R0i*ncx + R1i*ncy) + R2i*ncz;  nn = (n0*n0 + n1*n1) + n2*n2;
+ *     not used unless nn > 0 and finite;  w = conf[py][px]/255.0;  with prev (nullable [N][3]) and prev[i] != (0, 0, 0):
+ *     r2 = ((n0*p0 + n1*p1) + n2*p2)^2 / nn, w = w*(s2/(s2 + r2));  g = w/nn;
+ *     M[i] += g*(n0n0, n0n1, n0n2, n1n1, n1n2, n2n2) (product, times g, added), wsum[i] += w, count[i] += 1, views in index order.
+ *   One lane per point with the view loop inside it: the sums have that order, bitwise repeatable and equal to the numpy path.
+ *   _solve: with the eigenvalues l0 <= l1 <= l2 of M[i] (cyclic Jacobi), d[i] = the unit eigenvector of l0, its component of largest
+ *   magnitude positive (lowest index on a tie), coherence[i] = (l1 - l0)/(l1 + l0), 0 where the denominator is not > 0; d = 0 and
+ *   coherence = 0 where count[i] < min_views, l1 <= 0 or an entry of M[i] is not finite.
+ *   Errors before any launch: a null buffer, V outside 1..4096, min_conf outside 0..255, min_views < 2, s2 not finite and positive
+ *   while prev is given.  N == 0 launches nothing.  The kernels trust the offsets: the caller (hgs_runtime.lift_check) guarantees
+ *   mask_offset + W*H lies inside masks, orients and confs, and that tab_dev holds 512 doubles. */
+int hgs_lift_moments(void* stream, long long N, const double* points, int V, const HgsCarveView* views_dev, const unsigned char* masks,
+                     const unsigned char* orients, const unsigned char* confs, const double* tab_dev, const double* prev, double s2,
+                     int min_conf, double* M, double* wsum, int* count);
+int hgs_lift_solve(void* stream, long long N, const double* M, const int* count, int min_views, double* d, double* coherence);
+
 /* Strand metrics (csrc/hgs_metrics.hip) <-> pct_matched_points of the reference's loss/metrics.py:12-85: the cKDTree
  *   query_ball_point per (distance, angle) pair, the direction test and the per-point Python loop that counts matches and
  *   strand-consistency votes.  Points and directions are float64 [n][3]; thresholds_host[K][2] = (r_k, cos_k), 1 <= K <= 32;
