@@ -94,6 +94,8 @@ SIGNATURES = {
     "hgs_carve_shell": (ci, [vp, ci, ci, ci, vp, vp]),
     "hgs_lift_moments": (ci, [vp, C.c_longlong, vp, ci, vp, vp, vp, vp, vp, vp, C.c_double, ci, vp, vp, vp]),
     "hgs_lift_solve": (ci, [vp, C.c_longlong, vp, vp, ci, vp, vp]),
+    "hgs_scalp_depth": (ci, [vp, ci, vp, ci, vp, ci, vp, vp, vp]),
+    "hgs_scalp_votes": (ci, [vp, C.c_longlong, vp, vp, ci, vp, vp, vp, C.c_double, C.c_double, vp, vp]),
     "hgs_oriented_match_scratch_bytes": (sz, [ci]),
     "hgs_oriented_match": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, sz]),
     "hgs_strand_votes": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]),
@@ -339,6 +341,27 @@ def lift_check(records, views_dev, masks, orients, confs, tab, images=None):
     require_device_buffer(tab, "tab", torch.float64)
     if tab.numel() != 512:
         raise HgsError(f"the sine / cosine table holds {tab.numel()} values, 256 x 2 expected")
+    return V
+
+
+def scalp_check(records, views_dev, masks, depth, faces=None, n_verts=None):
+    """What hgs_scalp_* may not be called without (include/hgs.h): carve_check's guarantee for the masks, extended to the float64 depth
+    buffer (addressed by the same mask_offset, in elements), views of fewer than 2^31 pixels and, with `faces` (an int32 device tensor
+    [F, 3]), indices inside the n_verts vertices.  Returns the number of views."""
+    import torch
+    V = carve_check(records, views_dev, masks)
+    require_device_buffer(depth, "depth", torch.float64)
+    for k in range(V):
+        r = records[k]
+        if r.W * r.H >= 1 << 31:
+            raise HgsError(f"view {k}: {r.W} x {r.H} pixels (fewer than 2^31)")
+        if r.mask_offset + r.W * r.H > depth.numel():
+            raise HgsError(f"view {k}: its depth map (offset {r.mask_offset}, {r.W} x {r.H}) does not lie inside the depth buffer of "
+                           f"{depth.numel()} values")
+    if faces is not None:
+        require_device_buffer(faces, "faces", torch.int32)
+        if faces.numel() and (int(faces.min()) < 0 or int(faces.max()) >= int(n_verts)):
+            raise HgsError(f"a face index is out of range of the {n_verts} vertices")
     return V
 
 

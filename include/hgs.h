@@ -707,6 +707,32 @@ int hgs_lift_moments(void* stream, long long N, const double* points, int V, con
                      int min_conf, double* M, double* wsum, int* count);
 int hgs_lift_solve(void* stream, long long N, const double* M, const int* count, int min_views, double* d, double* coherence);
 
+/* hgs_scalp_depth / hgs_scalp_votes (csrc/hgs_scalp.hip) <-> the scalp labelled on a capture's head mesh from its hair masks (utils/scalp.py
+ *   states the contract, init_scalp.py is the driver; the reference takes FLAME's fixed scalp region).  The views are HgsCarveView records;
+ *   `depth` is ONE buffer of doubles that holds view k's map [H][W] at ELEMENT offset mask_offset: the masks' layout with 8-byte elements.
+ *   All float64, one rounding per operation in this order, with xc, yc, zc, u, v, seen, px, py as in hgs_carve_votes.
+ *   _depth: sets every map to +inf and *dropped to 0 (a launch of its own in front), then for every face (verts[NV][3], faces[F][3], int32
+ *   indices in 0..NV-1) and view, with (xc_i, yc_i, zc_i), (u_i, v_i) of the vertices i = 0, 1, 2:
+ *     dropped, and counted in *dropped, when a zc_i is not > 0 or a u_i, v_i is not finite (no near-plane clipping);
+ *     candidates max(0, ceil(min u - 0.5)) <= px <= min(W - 1, floor(max u - 0.5)), likewise py; centre (cx, cy) = (px + 0.5, py + 0.5);
+ *     E0 = (u2 - u1)*(cy - v1) - (v2 - v1)*(cx - u1), E1 = (u0 - u2)*(cy - v2) - (v0 - v2)*(cx - u2),
+ *     E2 = (u1 - u0)*(cy - v0) - (v1 - v0)*(cx - u0), S = (E0 + E1) + E2;  covered iff S != 0 and (every E >= 0 or every E <= 0);
+ *     iz = (E0*(1/zc0) + E1*(1/zc1)) + E2*(1/zc2), z = S/iz;  Z[py][px] = min(Z[py][px], z) where covered and 0 < z < inf
+ *   (an atomic minimum on z's bit pattern: exact and order-free, the maps are bitwise reproducible).  F == 0 only sets the maps.
+ *   _votes: for the sample (points[i], normals[i]) over the V views:
+ *     nc_r = (R_r0*n0 + R_r1*n1) + R_r2*n2;  d = -((nc0*xc + nc1*yc) + nc2*zc);  nn = (nc0*nc0 + nc1*nc1) + nc2*nc2;
+ *     pp = (xc*xc + yc*yc) + zc*zc;  facing iff d > 0 and d*d >= (min_cos*min_cos)*(nn*pp);
+ *     visible iff seen and facing and zc <= Z[py][px] + depth_tol;  vis[i] += visible, hits[i] += visible and mask[py][px] != 0.
+ *   N == 0 launches nothing.
+ *   Errors before any launch, the text beginning with the function's name: a null buffer, V outside 1..4096, NV or F outside 0..2^24
+ *   (or faces without a vertex), min_cos outside [0, 1], depth_tol not finite or negative.  The kernels trust the offsets and the
+ *   indices: the caller (hgs_runtime.scalp_check) guarantees that mask_offset + W*H lies inside masks and depth, W*H < 2^31 and
+ *   0 <= faces < NV. */
+int hgs_scalp_depth(void* stream, int NV, const double* verts, int F, const int* faces, int V, const HgsCarveView* views_dev, double* depth,
+                    unsigned long long* dropped);
+int hgs_scalp_votes(void* stream, long long N, const double* points, const double* normals, int V, const HgsCarveView* views_dev,
+                    const unsigned char* masks, const double* depth, double min_cos, double depth_tol, int* vis, int* hits);
+
 /* Strand metrics (csrc/hgs_metrics.hip) <-> pct_matched_points of the reference's loss/metrics.py:12-85: the cKDTree
  *   query_ball_point per (distance, angle) pair, the direction test and the per-point Python loop that counts matches and
  *   strand-consistency votes.  Points and directions are float64 [n][3]; thresholds_host[K][2] = (r_k, cos_k), 1 <= K <= 32;
