@@ -2,11 +2,8 @@
 // driver): hgs_carve_votes, hgs_carve_grid, hgs_carve_shell.  gfx950, wave64.
 //
 // The contract (one definition for the numpy path, these kernels and the tests' loop restatement).  A view k is a pinhole camera with
-// its pose, R row-major world -> camera, and a uint8 mask [H][W].  Vote of the point (x, y, z) in view k, all float64, one rounding per
-// operation in the order written (this file is built with -ffp-contract=off):
-//   xc = ((R00*x + R01*y) + R02*z) + tx        (yc, zc likewise, rows 1 and 2)
-//   u  = fx*(xc/zc) + cx,   v = fy*(yc/zc) + cy
-//   seen iff zc > 0 and 0 <= u < W and 0 <= v < H      (any NaN: not seen);   px = floor(u), py = floor(v)
+// a uint8 mask [H][W].  Vote of the point (x, y, z) in view k (this file is built with -ffp-contract=off):
+//   xc, yc, zc, u, v, seen, px, py as in hgs_pinhole.h
 //   hit  iff seen and mask[py][px] != 0
 // seen[i], hits[i] are the counts over the views, rgb_sum[i][c] the sum of image[py][px][c] over the views that hit: integer sums,
 // exact and independent of order.  Keep rule, integers min_views >= 1 and 0 <= min_percent <= 100:
@@ -21,6 +18,7 @@
 // bound on the final integers, so occ is what the full counts give (tests/test_carve_gpu.py holds it to hgs_carve_votes' counts).
 // hgs_carve_votes has no early exit: its counts are the contract.  No atomics, no LDS.
 #include "hgs_common.h"
+#include "hgs_pinhole.h"
 
 #define HGS_CARVE_BX 64
 #define HGS_CARVE_BY 4
@@ -28,19 +26,6 @@
 #define HGS_CARVE_MAX_VIEWS 4096
 
 namespace {
-
-struct Vote { bool seen; size_t pixel; };   // pixel: py*W + px of a seen point
-
-__device__ __forceinline__ Vote carve_vote(const HgsCarveView& c, double x, double y, double z) {
-  const double xc = ((c.R[0] * x + c.R[1] * y) + c.R[2] * z) + c.t[0];
-  const double yc = ((c.R[3] * x + c.R[4] * y) + c.R[5] * z) + c.t[1];
-  const double zc = ((c.R[6] * x + c.R[7] * y) + c.R[8] * z) + c.t[2];
-  const double u = c.fx * (xc / zc) + c.cx, v = c.fy * (yc / zc) + c.cy;
-  Vote r = {false, 0};
-  r.seen = zc > 0.0 && u >= 0.0 && u < (double)c.W && v >= 0.0 && v < (double)c.H;   // (false for a NaN)
-  if (r.seen) r.pixel = (size_t)(int)floor(v) * (size_t)c.W + (size_t)(int)floor(u);   // px in [0, W - 1], py in [0, H - 1]
-  return r;
-}
 
 __global__ __launch_bounds__(256) void carve_votes_kernel(long long N, const double* __restrict__ points, int V,
                                                           const HgsCarveView* __restrict__ views, const unsigned char* __restrict__ masks,
@@ -52,13 +37,14 @@ __global__ __launch_bounds__(256) void carve_votes_kernel(long long N, const dou
   int seen = 0, hits = 0, r = 0, g = 0, b = 0;
   for (int k = 0; k < V; k++) {
     const HgsCarveView& c = views[k];
-    const Vote vt = carve_vote(c, x, y, z);
-    if (!vt.seen) continue;
+    const Pinhole q = pinhole_project(c, x, y, z);
+    if (!pinhole_seen(&c, q)) continue;
     seen++;
-    if (masks[(size_t)c.mask_offset + vt.pixel] == 0) continue;
+    const size_t pixel = pinhole_pixel(c, q);
+    if (masks[(size_t)c.mask_offset + pixel] == 0) continue;
     hits++;
     if (images && c.image_offset >= 0) {
-      const unsigned char* __restrict__ p = images + (size_t)c.image_offset + 3 * vt.pixel;
+      const unsigned char* __restrict__ p = images + (size_t)c.image_offset + 3 * pixel;
       r += p[0]; g += p[1]; b += p[2];
     }
   }
@@ -80,10 +66,10 @@ __global__ __launch_bounds__(HGS_CARVE_BX * HGS_CARVE_BY) void carve_grid_kernel
   bool decided = false, kept = false;
   for (int k = 0; k < V; k++) {
     const HgsCarveView& c = views[k];
-    const Vote vt = carve_vote(c, x, y, z);
-    if (vt.seen) {
+    const Pinhole q = pinhole_project(c, x, y, z);
+    if (pinhole_seen(&c, q)) {
       seen++;
-      if (masks[(size_t)c.mask_offset + vt.pixel] != 0) hits++;
+      if (masks[(size_t)c.mask_offset + pinhole_pixel(c, q)] != 0) hits++;
     }
     const int left = V - 1 - k, most = seen + left;                 // most: the largest `seen` the voxel can still end with
     if (most < min_views || 100 * (seen - hits) > slack * most) { decided = true; kept = false; break; }

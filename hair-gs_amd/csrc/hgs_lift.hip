@@ -1,11 +1,11 @@
 // hgs_lift.hip -- 3-D hair directions lifted from a capture's 2-D orientation maps (utils/lift.py states the contract, init_cloud.py
 // --directions is the scene driver): hgs_lift_moments, hgs_lift_solve.  gfx950, wave64.
 //
-// The contract (one definition for the numpy path, these kernels and the tests' loop restatement).  A view k is a pinhole camera with
-// its pose, R row-major world -> camera, and three uint8 planes [H][W] at the record's mask_offset of three buffers: mask, orient and
-// conf.  TAB[256][2] = (sin, cos)(o*pi/255), float64, built on the host: no transcendental is evaluated here.  Term of the point
-// (x, y, z) in view k, all float64, one rounding per operation in the order written (this file is built with -ffp-contract=off):
-//   xc, yc, zc, u, v, seen, px, py as in hgs_carve.hip
+// The contract (one definition for the numpy path, these kernels and the tests' loop restatement).  A view k is a pinhole camera
+// with three uint8 planes [H][W] at the record's mask_offset of three buffers: mask, orient and conf.  TAB[256][2] =
+// (sin, cos)(o*pi/255), float64, built on the host: no transcendental is evaluated here.  Term of the point (x, y, z) in view k, all
+// float64, one rounding per operation in the order written (this file is built with -ffp-contract=off):
+//   xc, yc, zc, u, v, seen, px, py as in hgs_pinhole.h
 //   used iff seen and mask[py][px] != 0 and conf[py][px] >= min_conf
 //   lu = TAB[orient[py][px]][0], lv = TAB[..][1];  a = lu/fx, b = lv/fy
 //   ncx = -(zc*b), ncy = zc*a, ncz = xc*b - yc*a;  n_i = (R0i*ncx + R1i*ncy) + R2i*ncz;  nn = (n0*n0 + n1*n1) + n2*n2
@@ -19,12 +19,13 @@
 // Work split.  One lane per point in both kernels.  hgs_lift_moments runs the view loop inside the lane, so a point's sums have the
 // contract's order whatever the launch looks like: bitwise repeatable, and equal to the numpy path.  The view record is indexed by
 // the loop counter alone (wavefront-uniform: scalar loads); TAB is indexed by the sampled byte, which differs from lane to lane, so
-// the workgroup copies its 4 KiB into LDS once.  hgs_lift_solve is cyclic Jacobi on the 3 x 3 matrix in registers (scalars and ?:
-// selects, nothing indexed at run time), the rotation of csrc/hgs_normals.hip.  No atomics.
+// the workgroup copies its 4 KiB into LDS once.  hgs_lift_solve is cyclic Jacobi on the 3 x 3 matrix in registers (hgs_jacobi3.h,
+// shared with csrc/hgs_normals.hip).  No atomics.
 #include "hgs_common.h"
+#include "hgs_jacobi3.h"
+#include "hgs_pinhole.h"
 
 #define HGS_LIFT_MAX_VIEWS 4096
-#define HGS_LIFT_JACOBI_SWEEPS 12     // upper bound; a 3 x 3 matrix is diagonal to the last bit after 4-6
 
 namespace {
 
@@ -48,18 +49,15 @@ __global__ __launch_bounds__(256) void lift_moments_kernel(long long N, const do
   int count = 0;
   for (int k = 0; k < V; k++) {
     const HgsCarveView& c = views[k];
-    const double xc = ((c.R[0] * x + c.R[1] * y) + c.R[2] * z) + c.t[0];
-    const double yc = ((c.R[3] * x + c.R[4] * y) + c.R[5] * z) + c.t[1];
-    const double zc = ((c.R[6] * x + c.R[7] * y) + c.R[8] * z) + c.t[2];
-    const double u = c.fx * (xc / zc) + c.cx, v = c.fy * (yc / zc) + c.cy;
-    if (!(zc > 0.0 && u >= 0.0 && u < (double)c.W && v >= 0.0 && v < (double)c.H)) continue;   // (a NaN: not seen)
-    const size_t at = (size_t)c.mask_offset + ((size_t)(int)floor(v) * (size_t)c.W + (size_t)(int)floor(u));   // px in [0, W - 1], py in [0, H - 1]
+    const Pinhole q = pinhole_project(c, x, y, z);
+    if (!pinhole_seen(&c, q)) continue;
+    const size_t at = (size_t)c.mask_offset + pinhole_pixel(c, q);
     if (masks[at] == 0) continue;
     const int cf = confs[at];
     if (cf < min_conf) continue;
     const int o = orients[at];
     const double a = stab[2 * o] / c.fx, b = stab[2 * o + 1] / c.fy;
-    const double ncx = -(zc * b), ncy = zc * a, ncz = xc * b - yc * a;
+    const double ncx = -(q.zc * b), ncy = q.zc * a, ncz = q.xc * b - q.yc * a;
     const double n0 = (c.R[0] * ncx + c.R[3] * ncy) + c.R[6] * ncz;
     const double n1 = (c.R[1] * ncx + c.R[4] * ncy) + c.R[7] * ncz;
     const double n2 = (c.R[2] * ncx + c.R[5] * ncy) + c.R[8] * ncz;
@@ -83,36 +81,6 @@ __global__ __launch_bounds__(256) void lift_moments_kernel(long long N, const do
   count_out[i] = count;
 }
 
-// One Jacobi rotation that annihilates a_pq of a symmetric 3 x 3 matrix (r: the third index); V's columns follow.  (The rotation of
-// csrc/hgs_normals.hip, kept as a copy so that file compiles to what it did.)
-__device__ __forceinline__ void lift_jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p,
-                                                   double& v0q, double& v1p, double& v1q, double& v2p, double& v2q, bool late) {
-  if (apq == 0.0) return;
-  const double g = 100.0 * fabs(apq);
-  if (late && fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) { apq = 0.0; return; }
-  const double h = aqq - app;
-  double t;
-  if (fabs(h) + g == fabs(h)) {
-    t = apq / h;
-  } else {
-    const double th = 0.5 * h / apq;
-    t = 1.0 / (fabs(th) + sqrt(1.0 + th * th));
-    if (th < 0.0) t = -t;
-  }
-  const double c = 1.0 / sqrt(1.0 + t * t), s = t * c, tau = s / (1.0 + c);
-  const double hh = t * apq;
-  app = app - hh;
-  aqq = aqq + hh;
-  apq = 0.0;
-  const double p0 = arp, q0 = arq;
-  arp = p0 - s * (q0 + p0 * tau);
-  arq = q0 + s * (p0 - q0 * tau);
-  double a, b;
-  a = v0p; b = v0q; v0p = a - s * (b + a * tau); v0q = b + s * (a - b * tau);
-  a = v1p; b = v1q; v1p = a - s * (b + a * tau); v1q = b + s * (a - b * tau);
-  a = v2p; b = v2q; v2p = a - s * (b + a * tau); v2q = b + s * (a - b * tau);
-}
-
 __global__ __launch_bounds__(256) void lift_solve_kernel(long long N, const double* __restrict__ M, const int* __restrict__ count,
                                                          int min_views, double* __restrict__ d, double* __restrict__ coherence) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -123,14 +91,8 @@ __global__ __launch_bounds__(256) void lift_solve_kernel(long long N, const doub
   const double big = __builtin_inf();
   const bool finite = fabs(a00) < big && fabs(a01) < big && fabs(a02) < big && fabs(a11) < big && fabs(a12) < big && fabs(a22) < big;
   if (finite && count[i] >= min_views) {
-    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
-    for (int s = 0; s < HGS_LIFT_JACOBI_SWEEPS; s++) {
-      if (fabs(a01) + fabs(a02) + fabs(a12) == 0.0) break;
-      const bool late = s >= 3;
-      lift_jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21, late);
-      lift_jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22, late);
-      lift_jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22, late);
-    }
+    double v00, v01, v02, v10, v11, v12, v20, v21, v22;
+    jacobi3_sweeps(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
     // column of the smallest eigenvalue (lowest index on a tie), and the middle eigenvalue
     const int lo = a00 <= a11 ? (a22 < a00 ? 2 : 0) : (a22 < a11 ? 2 : 1);
     const double l0 = lo == 0 ? a00 : (lo == 1 ? a11 : a22);

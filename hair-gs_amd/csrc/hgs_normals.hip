@@ -23,13 +23,13 @@
 #include <float.h>
 
 #include "hgs_common.h"
+#include "hgs_jacobi3.h"
 #include "hgs_keysort.h"
 
 #define NRM_MAX_K 64
 #define NRM_MAX_N (1 << 27)      // keys, sorted positions and cell bounds are 32-bit; the padded key count must fit an int
 #define NRM_MAX_LEVEL 7          // 2 M cells of 8 bytes
 #define NRM_MM_BLOCKS 64
-#define NRM_JACOBI_SWEEPS 12     // upper bound; a 3 x 3 matrix is diagonal to the last bit after 4-6
 
 namespace {
 
@@ -158,35 +158,6 @@ __device__ __forceinline__ double uniform_f64(double v) {    // a value that is 
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
-// One Jacobi rotation that annihilates a_pq of a symmetric 3 x 3 matrix (r: the third index); V's columns follow.
-__device__ __forceinline__ void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
-                                              double& v1p, double& v1q, double& v2p, double& v2q, bool late) {
-  if (apq == 0.0) return;
-  const double g = 100.0 * fabs(apq);
-  if (late && fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) { apq = 0.0; return; }
-  const double h = aqq - app;
-  double t;
-  if (fabs(h) + g == fabs(h)) {
-    t = apq / h;
-  } else {
-    const double th = 0.5 * h / apq;
-    t = 1.0 / (fabs(th) + sqrt(1.0 + th * th));
-    if (th < 0.0) t = -t;
-  }
-  const double c = 1.0 / sqrt(1.0 + t * t), s = t * c, tau = s / (1.0 + c);
-  const double hh = t * apq;
-  app = app - hh;
-  aqq = aqq + hh;
-  apq = 0.0;
-  const double p0 = arp, q0 = arq;
-  arp = p0 - s * (q0 + p0 * tau);
-  arq = q0 + s * (p0 - q0 * tau);
-  double a, b;
-  a = v0p; b = v0q; v0p = a - s * (b + a * tau); v0q = b + s * (a - b * tau);
-  a = v1p; b = v1q; v1p = a - s * (b + a * tau); v1q = b + s * (a - b * tau);
-  a = v2p; b = v2q; v2p = a - s * (b + a * tau); v2q = b + s * (a - b * tau);
-}
-
 __global__ __launch_bounds__(256) void normals_kernel(int N, int K, int L, const double* __restrict__ pts,
                                                       const NrmPoint* __restrict__ sorted, const uint2* __restrict__ cells,
                                                       const NrmGrid* __restrict__ grid, double* __restrict__ normals,
@@ -267,14 +238,8 @@ __global__ __launch_bounds__(256) void normals_kernel(int N, int K, int L, const
   const double x = in ? qx - mx : 0.0, y = in ? qy - my : 0.0, z = in ? qz - mz : 0.0;
   double a00 = wave_sum(x * x) * invK, a01 = wave_sum(x * y) * invK, a02 = wave_sum(x * z) * invK;
   double a11 = wave_sum(y * y) * invK, a12 = wave_sum(y * z) * invK, a22 = wave_sum(z * z) * invK;
-  double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
-  for (int s = 0; s < NRM_JACOBI_SWEEPS; s++) {
-    if (fabs(a01) + fabs(a02) + fabs(a12) == 0.0) break;    // (the same in every lane)
-    const bool late = s >= 3;
-    jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21, late);
-    jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22, late);
-    jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22, late);
-  }
+  double v00, v01, v02, v10, v11, v12, v20, v21, v22;
+  jacobi3_sweeps(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);   // (the same path in every lane)
   const int m = a00 <= a11 ? (a22 < a00 ? 2 : 0) : (a22 < a11 ? 2 : 1);
   double nx = m == 0 ? v00 : (m == 1 ? v01 : v02), ny = m == 0 ? v10 : (m == 1 ? v11 : v12), nz = m == 0 ? v20 : (m == 1 ? v21 : v22);
   const double len = sqrt((nx * nx + ny * ny) + nz * nz);

@@ -2,7 +2,7 @@
 // init_scalp.py is the scene driver): hgs_scalp_depth, hgs_scalp_votes.  gfx950, wave64.
 //
 // The contract (one definition for the numpy path, these kernels and the tests' loop restatement).  Views are HgsCarveView records;
-// xc, yc, zc, u, v, seen, px, py of a point are hgs_carve_votes'.  All float64, one rounding per operation in the order written (this
+// xc, yc, zc, u, v, seen, px, py of a point as in hgs_pinhole.h.  All float64, one rounding per operation in the order written (this
 // file is built with -ffp-contract=off).
 // Depth map of view k, Z[H][W], +inf to begin with.  For a face with (xc_i, yc_i, zc_i), (u_i, v_i) of its vertices i = 0, 1, 2:
 //   dropped (and counted) when a zc_i is not > 0 or a u_i, v_i is not finite
@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "hgs_common.h"
+#include "hgs_pinhole.h"
 
 #define HGS_SCALP_MAX_VIEWS 4096
 #define HGS_SCALP_MAX_VERTS (1 << 24)
@@ -36,16 +37,6 @@
 #define HGS_SCALP_INF_BITS 0x7FF0000000000000ull
 
 namespace {
-
-struct Cam { double xc, yc, zc; };
-
-__device__ __forceinline__ Cam scalp_camera(const HgsCarveView& c, double x, double y, double z) {
-  Cam r;
-  r.xc = ((c.R[0] * x + c.R[1] * y) + c.R[2] * z) + c.t[0];
-  r.yc = ((c.R[3] * x + c.R[4] * y) + c.R[5] * z) + c.t[1];
-  r.zc = ((c.R[6] * x + c.R[7] * y) + c.R[8] * z) + c.t[2];
-  return r;
-}
 
 __device__ __forceinline__ bool scalp_finite(double a) { return a - a == 0.0; }   // (false for NaN and both infinities)
 
@@ -75,9 +66,9 @@ __global__ __launch_bounds__(64) void scalp_depth_kernel(const double* __restric
     bool ok = true;
     for (int i = 0; i < 3; i++) {
       const double* __restrict__ p = verts + 3 * (size_t)faces[3 * (size_t)f + i];   // (the caller guarantees 0 <= index < NV)
-      const Cam q = scalp_camera(c, p[0], p[1], p[2]);
-      u[i] = c.fx * (q.xc / q.zc) + c.cx;
-      v[i] = c.fy * (q.yc / q.zc) + c.cy;
+      const Pinhole q = pinhole_project(c, p[0], p[1], p[2]);
+      u[i] = q.u;
+      v[i] = q.v;
       iz[i] = 1.0 / q.zc;
       ok = ok && q.zc > 0.0 && scalp_finite(u[i]) && scalp_finite(v[i]);
     }
@@ -138,16 +129,15 @@ __global__ __launch_bounds__(256) void scalp_votes_kernel(long long N, const dou
   int vis = 0, hits = 0;
   for (int k = 0; k < V; k++) {
     const HgsCarveView& c = views[k];
-    const Cam q = scalp_camera(c, x, y, z);
-    const double u = c.fx * (q.xc / q.zc) + c.cx, v = c.fy * (q.yc / q.zc) + c.cy;
-    if (!(q.zc > 0.0 && u >= 0.0 && u < (double)c.W && v >= 0.0 && v < (double)c.H)) continue;   // not seen (a NaN included)
+    const Pinhole q = pinhole_project(c, x, y, z);
+    if (!pinhole_seen(&c, q)) continue;
     const double nc0 = (c.R[0] * n0 + c.R[1] * n1) + c.R[2] * n2;
     const double nc1 = (c.R[3] * n0 + c.R[4] * n1) + c.R[5] * n2;
     const double nc2 = (c.R[6] * n0 + c.R[7] * n1) + c.R[8] * n2;
     const double d = -((nc0 * q.xc + nc1 * q.yc) + nc2 * q.zc);
     const double nn = (nc0 * nc0 + nc1 * nc1) + nc2 * nc2, pp = (q.xc * q.xc + q.yc * q.yc) + q.zc * q.zc;
     if (!(d > 0.0 && d * d >= cos2 * (nn * pp))) continue;          // not facing
-    const size_t pixel = (size_t)(int)floor(v) * (size_t)c.W + (size_t)(int)floor(u);   // px in [0, W - 1], py in [0, H - 1]
+    const size_t pixel = pinhole_pixel(c, q);
     if (!(q.zc <= depth[(size_t)c.mask_offset + pixel] + depth_tol)) continue;          // hidden
     vis++;
     if (masks[(size_t)c.mask_offset + pixel] != 0) hits++;

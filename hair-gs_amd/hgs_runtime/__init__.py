@@ -8,6 +8,8 @@ import ctypes as C
 import os
 import subprocess
 
+import numpy as np
+
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("HGS_LIB") or os.path.join(_PKG_ROOT, "libhgs.so")   # HGS_LIB: another build of the same ABI (A/B runs, tools/)
 CSRC = os.path.join(_PKG_ROOT, "csrc")
@@ -184,6 +186,9 @@ class CarveView(C.Structure):
                 ("cy", C.c_double), ("W", C.c_int32), ("H", C.c_int32), ("mask_offset", C.c_int64), ("image_offset", C.c_int64)]
 
 
+_CARVE_VIEW = np.dtype(CarveView)   # (a numpy view of a record array: _planes)
+
+
 class AdamInline(C.Structure):
     """include/hgs.h HgsAdamInline."""
     _fields_ = [("slot", AdamSlot * 6), ("beta1", cf), ("beta2", cf), ("eps", cf)]
@@ -299,10 +304,24 @@ def require_device_buffer(t, name, dtype):
     return t
 
 
-def carve_check(records, views_dev, masks, images=None):
-    """What hgs_carve_* may not be called without (include/hgs.h): `records`, the host copy (a CarveView array) of the view records in
-    views_dev, name a mask -- and, where image_offset >= 0, an image -- that lies inside its buffer; every buffer is a contiguous
-    uint8 device tensor.  Returns the number of views."""
+def _planes(records):
+    """[(mask_offset, W, H, image_offset)] of the view records as plain integers, read once through a numpy view of the array: a
+    field of a ctypes record costs far more than the comparison it feeds, and these checks run in front of every launch."""
+    a = np.frombuffer(records, dtype=_CARVE_VIEW)
+    return list(zip(a["mask_offset"].tolist(), a["W"].tolist(), a["H"].tolist(), a["image_offset"].tolist()))
+
+
+def _planes_inside(planes, buf, what, where):
+    """Every view's plane, W*H elements from its mask_offset, lies inside the device buffer `buf`; the refusal names the plane
+    (`what`) and the buffer (`where`)."""
+    n = buf.numel()
+    for k, (offset, W, H, _) in enumerate(planes):
+        if offset < 0 or offset + W * H > n:
+            raise HgsError(f"view {k}: its {what} (offset {offset}, {W} x {H}) does not lie inside the {where}")
+
+
+def _carve_planes(records, views_dev, masks, images):
+    """carve_check; returns _planes(records) for the checks that extend it."""
     import torch
     V = len(records)
     if not 1 <= V <= 4096:
@@ -313,16 +332,22 @@ def carve_check(records, views_dev, masks, images=None):
         require_device_buffer(images, "images", torch.uint8)
     if views_dev.numel() != V * C.sizeof(CarveView):
         raise HgsError(f"the view buffer holds {views_dev.numel()} bytes, {V} views take {V * C.sizeof(CarveView)}")
-    for k in range(V):
-        r = records[k]
-        if r.W < 1 or r.H < 1:
-            raise HgsError(f"view {k}: {r.W} x {r.H} pixels")
-        if r.mask_offset < 0 or r.mask_offset + r.W * r.H > masks.numel():
-            raise HgsError(f"view {k}: its mask (offset {r.mask_offset}, {r.W} x {r.H}) does not lie inside the mask buffer of "
-                           f"{masks.numel()} bytes")
-        if r.image_offset >= 0 and (images is None or r.image_offset + 3 * r.W * r.H > images.numel()):
-            raise HgsError(f"view {k}: its image (offset {r.image_offset}, {r.W} x {r.H} x 3) does not lie inside the image buffer")
-    return V
+    planes = _planes(records)
+    for k, (_, W, H, _) in enumerate(planes):
+        if W < 1 or H < 1:
+            raise HgsError(f"view {k}: {W} x {H} pixels")
+    _planes_inside(planes, masks, "mask", f"mask buffer of {masks.numel()} bytes")
+    for k, (_, W, H, image_offset) in enumerate(planes):
+        if image_offset >= 0 and (images is None or image_offset + 3 * W * H > images.numel()):
+            raise HgsError(f"view {k}: its image (offset {image_offset}, {W} x {H} x 3) does not lie inside the image buffer")
+    return planes
+
+
+def carve_check(records, views_dev, masks, images=None):
+    """What hgs_carve_* may not be called without (include/hgs.h): `records`, the host copy (a CarveView array) of the view records in
+    views_dev, name a mask -- and, where image_offset >= 0, an image -- that lies inside its buffer; every buffer is a contiguous
+    uint8 device tensor.  Returns the number of views."""
+    return len(_carve_planes(records, views_dev, masks, images))
 
 
 def lift_check(records, views_dev, masks, orients, confs, tab, images=None):
@@ -330,18 +355,14 @@ def lift_check(records, views_dev, masks, orients, confs, tab, images=None):
     orientation and confidence buffers (addressed by the same mask_offset), and a float64 table of 256 x 2 entries.  `images`: the
     image buffer of records that name one (the lift does not read it).  Returns the number of views."""
     import torch
-    V = carve_check(records, views_dev, masks, images)
+    planes = _carve_planes(records, views_dev, masks, images)
     for name, buf in (("orients", orients), ("confs", confs)):
         require_device_buffer(buf, name, torch.uint8)
-        for k in range(V):
-            r = records[k]
-            if r.mask_offset + r.W * r.H > buf.numel():
-                raise HgsError(f"view {k}: its plane (offset {r.mask_offset}, {r.W} x {r.H}) does not lie inside the {name} buffer of "
-                               f"{buf.numel()} bytes")
+        _planes_inside(planes, buf, "plane", f"{name} buffer of {buf.numel()} bytes")
     require_device_buffer(tab, "tab", torch.float64)
     if tab.numel() != 512:
         raise HgsError(f"the sine / cosine table holds {tab.numel()} values, 256 x 2 expected")
-    return V
+    return len(planes)
 
 
 def scalp_check(records, views_dev, masks, depth, faces=None, n_verts=None):
@@ -349,20 +370,17 @@ def scalp_check(records, views_dev, masks, depth, faces=None, n_verts=None):
     buffer (addressed by the same mask_offset, in elements), views of fewer than 2^31 pixels and, with `faces` (an int32 device tensor
     [F, 3]), indices inside the n_verts vertices.  Returns the number of views."""
     import torch
-    V = carve_check(records, views_dev, masks)
+    planes = _carve_planes(records, views_dev, masks, None)
     require_device_buffer(depth, "depth", torch.float64)
-    for k in range(V):
-        r = records[k]
-        if r.W * r.H >= 1 << 31:
-            raise HgsError(f"view {k}: {r.W} x {r.H} pixels (fewer than 2^31)")
-        if r.mask_offset + r.W * r.H > depth.numel():
-            raise HgsError(f"view {k}: its depth map (offset {r.mask_offset}, {r.W} x {r.H}) does not lie inside the depth buffer of "
-                           f"{depth.numel()} values")
+    for k, (_, W, H, _) in enumerate(planes):
+        if W * H >= 1 << 31:
+            raise HgsError(f"view {k}: {W} x {H} pixels (fewer than 2^31)")
+    _planes_inside(planes, depth, "depth map", f"depth buffer of {depth.numel()} values")
     if faces is not None:
         require_device_buffer(faces, "faces", torch.int32)
         if faces.numel() and (int(faces.min()) < 0 or int(faces.max()) >= int(n_verts)):
             raise HgsError(f"a face index is out of range of the {n_verts} vertices")
-    return V
+    return len(planes)
 
 
 KERNEL_COUNT = 18

@@ -57,17 +57,6 @@ def _fail(msg):
     raise SystemExit(f"init_cloud.py: {msg}")
 
 
-def _read_plane(path, view, what, mode):
-    from PIL import Image
-    if not os.path.exists(path):
-        _fail(f"{path} is missing ({what} of view {view.name})")
-    with Image.open(path) as im:
-        a = np.asarray(im.convert(mode))
-    if a.shape[:2] != (view.H, view.W):
-        _fail(f"{path}: {what} of {a.shape[1]} x {a.shape[0]} pixels, its camera has {view.W} x {view.H}")
-    return np.array(a)                                       # (a writable copy: PIL hands out a read-only view)
-
-
 def _stem(view):
     return os.path.basename(view.name).split(".")[0]             # (the loader's rule, data/dataset_readers.py)
 
@@ -78,9 +67,9 @@ def lift_normals(voter, orients, confs, xyz, args):
     if voter.device is None:
         d, coherence, _ = lift.lift_directions(xyz, voter.views, voter.masks, orients, confs, args.rounds, args.sigma_deg, args.min_conf)
     else:
-        import torch
+        from utils.views import upload_points
         packed = lift.pack(voter.views, voter.masks, orients, confs, voter.device, carve_packed=voter.packed)
-        pts = torch.from_numpy(np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)).to(voter.device)
+        pts = upload_points(xyz, voter.device)
         d, coherence, _ = (t.cpu().numpy() for t in lift.directions_device(pts, packed, args.rounds, args.sigma_deg, args.min_conf))
     return np.where((coherence >= args.min_coherence)[:, None], d, 0.0), coherence
 
@@ -115,8 +104,7 @@ class _Voter:
     def votes(self, points, with_rgb):
         if self.device is None:
             return self.carve.votes_numpy(points, self.views, self.masks, self.images if with_rgb else None)
-        import torch
-        pts = torch.from_numpy(np.ascontiguousarray(points, np.float64).reshape(-1, 3)).to(self.device)
+        pts = self.carve.upload_points(points, self.device)
         return tuple(t.cpu().numpy() for t in self.carve.votes_device(pts, self.packed, with_rgb=with_rgb))
 
 
@@ -180,8 +168,8 @@ def main(argv=None):
     parser.add_argument("--min_coherence", type=float, default=0.0, help="directions below this coherence are written as zero")
     args = parser.parse_args(argv)
     from data.colmap import read_points3D_binary, read_points3D_text, write_points3D_arrays
-    from undistort import read_sparse
     from utils import carve
+    from utils.views import load_views, read_plane
     if args.device not in ("cuda", "cpu"):
         _fail(f"--device {args.device}: cuda or cpu")
     if args.min_views < 1 or not 0 <= args.min_percent <= 100 or args.dilate < 0 or args.max_points < 1 or not 1 <= args.grid <= carve.MAX_DIM:
@@ -200,21 +188,18 @@ def main(argv=None):
             _fail(f"{result} is the result of an earlier run (COLMAP's points are in {os.path.basename(backup)}): pass --overwrite")
     else:
         original = next((os.path.join(sparse, n) for n in ("points3D.bin", "points3D.txt") if os.path.exists(os.path.join(sparse, n))), None)
-    cameras, images = read_sparse(sparse)
+    need_images = args.mode in ("hull", "both")
+    orients = confs = None
     try:
-        views = [carve.view_of(cameras[im.camera_id], im) for im in images.values()]
+        views = load_views(sparse)
+        masks = [read_plane(os.path.join(src, "masks", os.path.basename(v.name)), v, "the mask") for v in views]
+        imgs = [read_plane(os.path.join(src, args.images, os.path.basename(v.name)), v, "the image", "RGB") for v in views] if need_images else None
+        if args.directions:
+            folder = os.path.join(src, args.orientations)
+            orients = [read_plane(os.path.join(folder, f"{_stem(v)}_orientation.png"), v, "the orientation map") for v in views]
+            confs = [read_plane(os.path.join(folder, f"{_stem(v)}_confidence.png"), v, "the confidence map") for v in views]
     except ValueError as e:
         _fail(str(e))
-    if not 1 <= len(views) <= carve.MAX_VIEWS:
-        _fail(f"{len(views)} views (1 to {carve.MAX_VIEWS})")
-    need_images = args.mode in ("hull", "both")
-    masks = [_read_plane(os.path.join(src, "masks", os.path.basename(v.name)), v, "the mask", "L") for v in views]
-    imgs = [_read_plane(os.path.join(src, args.images, os.path.basename(v.name)), v, "the image", "RGB") for v in views] if need_images else None
-    orients = confs = None
-    if args.directions:
-        folder = os.path.join(src, args.orientations)
-        orients = [_read_plane(os.path.join(folder, f"{_stem(v)}_orientation.png"), v, "the orientation map", "L") for v in views]
-        confs = [_read_plane(os.path.join(folder, f"{_stem(v)}_confidence.png"), v, "the confidence map", "L") for v in views]
     voter = _Voter(views, masks, imgs, None if args.device == "cpu" else "cuda", args.dilate)
     parts = []
     if args.mode in ("filter", "both"):

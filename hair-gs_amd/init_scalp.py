@@ -35,18 +35,6 @@ def _fail(msg):
     raise SystemExit(f"init_scalp.py: {msg}")
 
 
-def read_mask(path, view):
-    """The uint8 [H, W] plane of a view's mask (converted to L, as the loader reads it)."""
-    from PIL import Image
-    if not os.path.exists(path):
-        _fail(f"{path} is missing (the mask of view {view.name})")
-    with Image.open(path) as im:
-        a = np.array(im.convert("L"))
-    if a.shape != (view.H, view.W):
-        _fail(f"{path}: a mask of {a.shape[1]} x {a.shape[0]} pixels, its camera has {view.W} x {view.H}")
-    return a
-
-
 def load_mesh(path):
     """(verts f64 [NV, 3], faces int64 [F, 3]) of an OBJ or a triangle PLY."""
     if not os.path.exists(path):
@@ -92,8 +80,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     from data.head_reconstruction_data import save_head_reconstruction_data_npz
     from init_cloud import select
-    from undistort import read_sparse
     from utils import carve, scalp
+    from utils.views import load_views, read_plane
     if args.device not in ("cuda", "cpu"):
         _fail(f"--device {args.device}: cuda or cpu")
     if args.min_views < 1 or not 0 <= args.min_percent <= 100 or args.dilate < 0 or args.max_points < 1 or not 0.0 <= args.min_cos <= 1.0 \
@@ -106,14 +94,11 @@ def main(argv=None):
     result, backup = os.path.join(src, RESULT), os.path.join(src, BACKUP)
     if os.path.exists(result) and not args.overwrite:
         _fail(f"{result} exists: pass --overwrite to replace it (the first file replaced is kept as {BACKUP})")
-    cameras, images = read_sparse(os.path.join(src, "sparse", "0"))
     try:
-        views = [carve.view_of(cameras[im.camera_id], im) for im in images.values()]
+        views = load_views(os.path.join(src, "sparse", "0"))
+        masks = [read_plane(os.path.join(src, "masks", os.path.basename(v.name)), v, "the mask", sized="a mask") for v in views]
     except ValueError as e:
         _fail(str(e))
-    if not 1 <= len(views) <= carve.MAX_VIEWS:
-        _fail(f"{len(views)} views (1 to {carve.MAX_VIEWS})")
-    masks = [read_mask(os.path.join(src, "masks", os.path.basename(v.name)), v) for v in views]
     verts, faces = load_mesh(args.mesh or os.path.join(src, "head_mesh.ply"))
     device = None if args.device == "cpu" else "cuda"
     if args.dilate:

@@ -5,16 +5,9 @@ scene driver; the reference starts Stage I from COLMAP's points, or from the FLA
 The contract (this module's numpy path, csrc/hgs_carve.hip and the tests' loop restatement state the same thing).  All arithmetic is
 float64 with one rounding per operation, in exactly the order written (the kernel file is built with -ffp-contract=off).
 
-View.  A PINHOLE or SIMPLE_PINHOLE camera of the sparse model with its image's pose: R = qvec2rotmat(qvec) (world -> camera,
-row-major), t = tvec, fx, fy, cx, cy (COLMAP's principal point, not the centred one the FoV cameras of training assume), W, H.  Any
-other camera model is refused by name: undistort.py makes pinholes of them.  A view's mask is the uint8 [H, W] plane of
-masks/<name> converted to L.  Views may differ in size.
+View.  The View of utils/views.py; its mask is the uint8 [H, W] plane of masks/<name> converted to L.  Views may differ in size.
 
-Vote of a point (x, y, z) in view k:
-    xc = ((R00*x + R01*y) + R02*z) + tx        (yc, zc likewise, rows 1 and 2)
-    u  = fx*(xc/zc) + cx,   v = fy*(yc/zc) + cy
-    seen  iff  zc > 0  and  0 <= u < W  and  0 <= v < H     (any NaN: not seen)
-    px = floor(u), py = floor(v)
+Vote of a point (x, y, z) in view k, with seen, px, py of utils/views.py's projection contract:
     hit   iff  seen and mask[py, px] != 0                   (the loader's rule: (mask/255).astype(bool))
 mask_votes(points f64 [N, 3], views, masks, images=None) returns, over all views, seen[N] and hits[N] as int32 and, with images
 (uint8 [H, W, 3]), rgb_sum[N, 3] as int32: the sum of the pixel (py, px) over the views that hit.  Integer sums: exact, and
@@ -48,45 +41,18 @@ device (values 0..255 and a maximum: no rounding).  Host plumbing around the ker
 
 device=None: numpy.  device="cuda": the kernels, on device tensors.  The caller chooses; neither falls back to the other (the
 convention of utils/normals.py and scene/strand_export.py)."""
-import collections
 import math
 
 import numpy as np
 
-from data.colmap import qvec2rotmat
+from utils.views import camera, check_views, is_cuda, pack, pixel, upload_points
+from utils.views import MAX_VIEWS, Packed, View, view_of  # noqa: F401  (what the carving's callers reach through this module)
 
 MAX_DIM = 1024
-MAX_VIEWS = 4096
 COARSE = 64
-PINHOLES = ("SIMPLE_PINHOLE", "PINHOLE")
-
-View = collections.namedtuple("View", ["R", "t", "fx", "fy", "cx", "cy", "W", "H", "name"])
 
 
-def view_of(camera, image):
-    """The View of a data.colmap Camera and Image."""
-    if camera.model not in PINHOLES:
-        raise ValueError(f"camera {camera.id} is a {camera.model} camera: the carving takes PINHOLE and SIMPLE_PINHOLE views only "
-                         "(undistort.py turns a distorted capture into one of pinholes)")
-    p = [float(v) for v in np.asarray(camera.params, np.float64).reshape(-1)]
-    fx, fy, cx, cy = (p[0], p[0], p[1], p[2]) if camera.model == "SIMPLE_PINHOLE" else (p[0], p[1], p[2], p[3])
-    return View(R=np.asarray(qvec2rotmat(np.asarray(image.qvec, np.float64)), np.float64), t=np.asarray(image.tvec, np.float64).reshape(3),
-                fx=fx, fy=fy, cx=cx, cy=cy, W=int(camera.width), H=int(camera.height), name=image.name)
-
-
-def _check_views(views, masks, images=None):
-    if not 1 <= len(views) <= MAX_VIEWS:
-        raise ValueError(f"{len(views)} views (1 to {MAX_VIEWS})")
-    if len(masks) != len(views) or (images is not None and len(images) != len(views)):
-        raise ValueError("one mask (and one image) per view")
-    for k, v in enumerate(views):
-        if masks[k].dtype != np.uint8 or masks[k].shape != (v.H, v.W):
-            raise ValueError(f"view {k} ({v.name}): a uint8 mask of {v.W} x {v.H} pixels expected, got {masks[k].dtype} {masks[k].shape}")
-        if images is not None and (images[k].dtype != np.uint8 or images[k].shape != (v.H, v.W, 3)):
-            raise ValueError(f"view {k} ({v.name}): a uint8 image [{v.H}, {v.W}, 3] expected, got {images[k].dtype} {images[k].shape}")
-
-
-def _check_rule(min_views, min_percent):
+def check_rule(min_views, min_percent):
     if int(min_views) != min_views or int(min_percent) != min_percent or min_views < 1 or not 0 <= min_percent <= 100:
         raise ValueError(f"min_views = {min_views} (an integer >= 1), min_percent = {min_percent} (an integer, 0 to 100)")
     return int(min_views), int(min_percent)
@@ -107,30 +73,15 @@ def keep(seen, hits, min_views, min_percent):
 
 
 # ---- numpy path ------------------------------------------------------------------------------------------------------
-def _project(view, x, y, z):
-    """(seen, py, px) of float64 arrays; py, px are 0 where not seen."""
-    R, t = view.R, view.t
-    with np.errstate(all="ignore"):
-        xc = ((R[0, 0] * x + R[0, 1] * y) + R[0, 2] * z) + t[0]
-        yc = ((R[1, 0] * x + R[1, 1] * y) + R[1, 2] * z) + t[1]
-        zc = ((R[2, 0] * x + R[2, 1] * y) + R[2, 2] * z) + t[2]
-        u = view.fx * (xc / zc) + view.cx
-        v = view.fy * (yc / zc) + view.cy
-        seen = (zc > 0.0) & (u >= 0.0) & (u < view.W) & (v >= 0.0) & (v < view.H)
-    px = np.floor(np.where(seen, u, 0.0)).astype(np.int64)
-    py = np.floor(np.where(seen, v, 0.0)).astype(np.int64)
-    return seen, py, px
-
-
 def votes_numpy(points, views, masks, images=None):
     points = np.asarray(points, np.float64).reshape(-1, 3)
-    _check_views(views, masks, images)
+    check_views(views, masks, images)
     N = points.shape[0]
     x, y, z = points[:, 0], points[:, 1], points[:, 2]
     seen, hits = np.zeros(N, np.int32), np.zeros(N, np.int32)
     rgb = np.zeros((N, 3), np.int32) if images is not None else None
     for k, view in enumerate(views):
-        s, py, px = _project(view, x, y, z)
+        s, py, px = pixel(view, *camera(view, x, y, z))
         hit = s & (masks[k][py, px] != 0)
         seen += s
         hits += hit
@@ -148,8 +99,8 @@ def centres(origin, h, dims):
 def grid_numpy(origin, h, dims, views, masks, min_views, min_percent):
     h = float(h)
     nx, ny, nz = _check_grid(h, dims)
-    min_views, min_percent = _check_rule(min_views, min_percent)
-    _check_views(views, masks)
+    min_views, min_percent = check_rule(min_views, min_percent)
+    check_views(views, masks)
     xs, ys, zs = centres(origin, h, (nx, ny, nz))
     occ = np.empty((nz, ny, nx), np.uint8)
     slab = max(1, (1 << 20) // (nx * ny))                       # z slices per pass: about 2^20 points
@@ -188,35 +139,6 @@ def dilate_numpy(mask, r):
 
 
 # ---- device path -----------------------------------------------------------------------------------------------------
-class Packed:
-    """The views of a capture on the device: records (the host copy, an hgs_runtime.CarveView array), views_dev (its bytes), masks_dev
-    and images_dev (or None): every mask / image flattened into one uint8 buffer, at the records' offsets."""
-
-    def __init__(self, records, views_dev, masks_dev, images_dev=None):
-        self.records, self.views_dev, self.masks_dev, self.images_dev = records, views_dev, masks_dev, images_dev
-
-
-def pack(views, masks, images=None, device="cuda"):
-    import ctypes
-    import torch
-    import hgs_runtime as rt
-    _check_views(views, masks, images)
-    records = (rt.CarveView * len(views))()
-    mask_offset = image_offset = 0
-    for k, v in enumerate(views):
-        r = records[k]
-        r.R[:] = [float(a) for a in np.asarray(v.R, np.float64).reshape(9)]
-        r.t[:] = [float(a) for a in np.asarray(v.t, np.float64).reshape(3)]
-        r.fx, r.fy, r.cx, r.cy, r.W, r.H = float(v.fx), float(v.fy), float(v.cx), float(v.cy), v.W, v.H
-        r.mask_offset, r.image_offset = mask_offset, image_offset if images is not None else -1
-        mask_offset += v.W * v.H
-        image_offset += 3 * v.W * v.H
-    raw = np.frombuffer(ctypes.string_at(ctypes.addressof(records), ctypes.sizeof(records)), np.uint8).copy()
-    masks_dev = torch.from_numpy(np.concatenate([m.reshape(-1) for m in masks])).to(device)
-    images_dev = torch.from_numpy(np.concatenate([im.reshape(-1) for im in images])).to(device) if images is not None else None
-    return Packed(records, torch.from_numpy(raw).to(device), masks_dev, images_dev)
-
-
 def votes_device(points, packed, with_rgb=False):
     """hgs_carve_votes on a float64 device tensor [N, 3]: (seen, hits) or (seen, hits, rgb_sum), int32 tensors on its device."""
     import torch
@@ -245,7 +167,7 @@ def grid_device(origin, h, dims, packed, min_views, min_percent):
     h = float(h)
     nx, ny, nz = _check_grid(h, dims, error=rt.HgsError)
     try:
-        min_views, min_percent = _check_rule(min_views, min_percent)
+        min_views, min_percent = check_rule(min_views, min_percent)
     except ValueError as e:
         raise rt.HgsError(str(e))
     origin = np.ascontiguousarray(np.asarray(origin, np.float64).reshape(3))
@@ -280,40 +202,30 @@ def dilate_device(mask, r):
 
 
 # ---- host-array entry points -----------------------------------------------------------------------------------------
-def _is_cuda(device):
-    if device is None:
-        return False
-    if not str(device).startswith("cuda"):
-        raise ValueError(f"device = {device!r}: None (numpy) or 'cuda' (the HIP kernels)")
-    return True
-
-
 def mask_votes(points, views, masks, images=None, device=None):
     """(seen, hits) int32 [N], and rgb_sum int32 [N, 3] with images; host arrays."""
-    if not _is_cuda(device):
+    if not is_cuda(device):
         return votes_numpy(points, views, masks, images)
-    import torch
-    pts = torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))).to(device)
-    out = votes_device(pts, pack(views, masks, images, device), with_rgb=images is not None)
+    out = votes_device(upload_points(points, device), pack(views, masks, images, device), with_rgb=images is not None)
     return tuple(t.cpu().numpy() for t in out)
 
 
 def carve_grid(origin, h, dims, views, masks, min_views, min_percent, device=None):
     """occ uint8 [nz, ny, nx], a host array."""
-    if not _is_cuda(device):
+    if not is_cuda(device):
         return grid_numpy(origin, h, dims, views, masks, min_views, min_percent)
     return grid_device(origin, h, dims, pack(views, masks, None, device), min_views, min_percent).cpu().numpy()
 
 
 def shell(occ, device=None):
-    if not _is_cuda(device):
+    if not is_cuda(device):
         return shell_numpy(occ)
     import torch
     return shell_device(torch.from_numpy(np.ascontiguousarray(occ)).to(device)).cpu().numpy()
 
 
 def dilate(mask, r, device=None):
-    if not _is_cuda(device):
+    if not is_cuda(device):
         return dilate_numpy(mask, r)
     import torch
     if mask.ndim != 2 or mask.dtype != np.uint8 or int(r) != r or r < 0:

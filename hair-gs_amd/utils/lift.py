@@ -5,16 +5,13 @@ driver, scene/gaussian_model.py direction_init the consumer; the reference start
 The contract (this module's numpy path, csrc/hgs_lift.hip and the tests' loop restatement state the same thing).  All arithmetic is
 float64 with one rounding per operation, in exactly the order written (the kernel file is built with -ffp-contract=off).
 
-Inputs per view k.  The View of utils/carve.py and three uint8 planes [H, W]: mask, orient and conf.  theta = orient*pi/255 and
+Inputs per view k.  The View of utils/views.py and three uint8 planes [H, W]: mask, orient and conf.  theta = orient*pi/255 and
 confidence = conf/255 (the loader's rule, data/dataset_readers.py).  The map's angle is the one the orientation loss compares
 against: theta = atan2(x, y) of the view-space direction, in [0, pi), measured from the image y axis, so the image line direction in
 pixel units is l = (lu, lv) = (sin theta, cos theta).  sin and cos come from a table TAB[256][2] = (sin, cos)(o*pi/255), built once
 on the host in float64 (table()) and handed to both backends: no transcendental is evaluated on the device.
 
-Sample of a point (x, y, z) in view k.  xc, yc, zc, u, v, seen, px, py exactly as in utils/carve.py:
-    xc = ((R00*x + R01*y) + R02*z) + tx        (yc, zc likewise, rows 1 and 2)
-    u  = fx*(xc/zc) + cx,   v = fy*(yc/zc) + cy
-    seen  iff  zc > 0  and  0 <= u < W  and  0 <= v < H     (any NaN: not seen);   px = floor(u), py = floor(v)
+Sample of a point (x, y, z) in view k.  xc, yc, zc, u, v, seen, px, py by utils/views.py's projection contract:
     used  iff  seen  and  mask[py, px] != 0  and  conf[py, px] >= min_conf       (min_conf: an integer, 0 to 255, default 1)
 
 The plane through the camera centre that contains the point's ray and the image line, with o = orient[py, px]:
@@ -55,7 +52,7 @@ import math
 
 import numpy as np
 
-from utils.carve import MAX_VIEWS, View, _check_views, _is_cuda, view_of  # noqa: F401  (View, view_of: re-exported for callers)
+from utils.views import camera, check_planes, check_views, is_cuda, pack as pack_views, pixel, upload_planes, upload_points
 
 
 def table():
@@ -72,14 +69,9 @@ def sin2(sigma_deg):
 
 
 def _check_planes(views, masks, orients, confs):
-    _check_views(views, masks)
-    for what, planes in (("orientation", orients), ("confidence", confs)):
-        if len(planes) != len(views):
-            raise ValueError(f"one {what} plane per view")
-        for k, v in enumerate(views):
-            if planes[k].dtype != np.uint8 or planes[k].shape != (v.H, v.W):
-                raise ValueError(f"view {k} ({v.name}): a uint8 {what} plane of {v.W} x {v.H} pixels expected, got {planes[k].dtype} "
-                                 f"{planes[k].shape}")
+    check_views(views, masks)
+    check_planes(views, orients, "orientation")
+    check_planes(views, confs, "confidence")
 
 
 def _check_knobs(min_conf=1, min_views=2):
@@ -98,24 +90,6 @@ def _check_prev(prev, N):
 
 
 # ---- numpy path ------------------------------------------------------------------------------------------------------
-def _camera(view, x, y, z):
-    R, t = view.R, view.t
-    xc = ((R[0, 0] * x + R[0, 1] * y) + R[0, 2] * z) + t[0]
-    yc = ((R[1, 0] * x + R[1, 1] * y) + R[1, 2] * z) + t[1]
-    zc = ((R[2, 0] * x + R[2, 1] * y) + R[2, 2] * z) + t[2]
-    return xc, yc, zc
-
-
-def _pixel(view, xc, yc, zc):
-    """(seen, py, px); py, px are 0 where not seen."""
-    u = view.fx * (xc / zc) + view.cx
-    v = view.fy * (yc / zc) + view.cy
-    seen = (zc > 0.0) & (u >= 0.0) & (u < view.W) & (v >= 0.0) & (v < view.H)
-    px = np.floor(np.where(seen, u, 0.0)).astype(np.int64)
-    py = np.floor(np.where(seen, v, 0.0)).astype(np.int64)
-    return seen, py, px
-
-
 def _accumulate(acc, view, cam, used, o, c, tab, prev, s2):
     """One view's term of the moments; acc = (M, wsum, count), updated in place."""
     M, wsum, count = acc
@@ -150,7 +124,7 @@ def _moments_loop(points, views, prev, s2, sample):
     acc = (np.zeros((N, 6), np.float64), np.zeros(N, np.float64), np.zeros(N, np.int32))
     with np.errstate(all="ignore"):
         for k, view in enumerate(views):
-            cam = _camera(view, x, y, z)
+            cam = camera(view, x, y, z)
             used, o, c = sample(k, view, cam)
             _accumulate(acc, view, cam, used, o.astype(np.int64), c.astype(np.float64), tab, prev, s2)
     return acc
@@ -161,7 +135,7 @@ def moments_numpy(points, views, masks, orients, confs, prev=None, s2=0.0, min_c
     min_conf, _ = _check_knobs(min_conf)
 
     def sample(k, view, cam):
-        seen, py, px = _pixel(view, *cam)
+        seen, py, px = pixel(view, *cam)
         c = confs[k][py, px]
         return seen & (masks[k][py, px] != 0) & (c >= min_conf), orients[k][py, px], c
     return _moments_loop(points, views, prev, s2, sample)
@@ -173,7 +147,7 @@ def moments_from_samples(points, views, used, orient, conf, prev=None, s2=0.0):
     used, orient, conf = np.asarray(used, bool), np.asarray(orient, np.uint8), np.asarray(conf, np.uint8)
 
     def sample(k, view, cam):
-        return used[k] & _pixel(view, *cam)[0], orient[k], conf[k]
+        return used[k] & pixel(view, *cam)[0], orient[k], conf[k]
     return _moments_loop(points, views, prev, s2, sample)
 
 
@@ -206,7 +180,7 @@ def solve_numpy(M, count, min_views=2):
 
 # ---- device path -----------------------------------------------------------------------------------------------------
 class Packed:
-    """A capture's views on the device for the lift: carve (a utils.carve.Packed: records, views_dev, masks_dev), orients_dev and
+    """A capture's views on the device for the lift: carve (a utils.views.Packed: records, views_dev, masks_dev), orients_dev and
     confs_dev (laid out like masks_dev, at the records' mask_offset) and tab_dev (TAB, float64 [256, 2])."""
 
     def __init__(self, carve, orients_dev, confs_dev, tab_dev):
@@ -214,14 +188,12 @@ class Packed:
 
 
 def pack(views, masks, orients, confs, device="cuda", carve_packed=None):
-    """carve_packed: the same views and masks already packed by utils.carve.pack (the driver's), reused as they are."""
+    """carve_packed: the same views and masks already packed by utils.views.pack (the driver's), reused as they are."""
     import torch
-    from utils import carve
     _check_planes(views, masks, orients, confs)
     if carve_packed is None:
-        carve_packed = carve.pack(views, masks, None, device)
-    flat = [torch.from_numpy(np.concatenate([p.reshape(-1) for p in planes])).to(device) for planes in (orients, confs)]
-    return Packed(carve_packed, flat[0], flat[1], torch.from_numpy(table()).to(device))
+        carve_packed = pack_views(views, masks, None, device)
+    return Packed(carve_packed, upload_planes(orients, device), upload_planes(confs, device), torch.from_numpy(table()).to(device))
 
 
 def moments_device(points, packed, prev=None, s2=0.0, min_conf=1):
@@ -283,24 +255,19 @@ def _check_rounds(rounds):
     return int(rounds)
 
 
-def _device_points(points, device):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))).to(device)
-
-
 def lift_moments(points, views, masks, orients, confs, prev=None, s2=0.0, min_conf=1, device=None):
     """(M f64 [N, 6], wsum f64 [N], count i32 [N]); host arrays."""
-    if not _is_cuda(device):
+    if not is_cuda(device):
         return moments_numpy(points, views, masks, orients, confs, prev, s2, min_conf)
-    pts = _device_points(points, device)
-    out = moments_device(pts, pack(views, masks, orients, confs, device), None if prev is None else _device_points(prev, device), s2,
+    pts = upload_points(points, device)
+    out = moments_device(pts, pack(views, masks, orients, confs, device), None if prev is None else upload_points(prev, device), s2,
                          min_conf)
     return tuple(t.cpu().numpy() for t in out)
 
 
 def lift_solve(M, count, min_views=2, device=None):
     """(d f64 [N, 3], coherence f64 [N]); host arrays."""
-    if not _is_cuda(device):
+    if not is_cuda(device):
         return solve_numpy(M, count, min_views)
     import torch
     M = torch.from_numpy(np.ascontiguousarray(np.asarray(M, np.float64).reshape(-1, 6))).to(device)
@@ -311,8 +278,8 @@ def lift_solve(M, count, min_views=2, device=None):
 def lift_directions(points, views, masks, orients, confs, rounds=3, sigma_deg=10.0, min_conf=1, min_views=2, device=None):
     """(d f64 [N, 3], coherence f64 [N], count i32 [N]) of the last round; host arrays."""
     rounds = _check_rounds(rounds)
-    if _is_cuda(device):
-        out = directions_device(_device_points(points, device), pack(views, masks, orients, confs, device), rounds, sigma_deg, min_conf,
+    if is_cuda(device):
+        out = directions_device(upload_points(points, device), pack(views, masks, orients, confs, device), rounds, sigma_deg, min_conf,
                                 min_views)
         return tuple(t.cpu().numpy() for t in out)
     s2 = sin2(sigma_deg)

@@ -5,10 +5,8 @@ scalp region, which ignores where this person's hairline is, and has nothing for
 
 The contract (this module's numpy path, csrc/hgs_scalp.hip and the loop restatement in tests/scalp_reference.py state the same thing).
 All arithmetic is float64 with one rounding per operation, in exactly the order written (the kernel file is built with
--ffp-contract=off).  Views are utils.carve.View records; the camera coordinates, u, v, seen, px and py of a point are utils.carve's:
-    xc = ((R00*x + R01*y) + R02*z) + tx        (yc, zc likewise, rows 1 and 2)
-    u  = fx*(xc/zc) + cx,   v = fy*(yc/zc) + cy
-    seen  iff  zc > 0  and  0 <= u < W  and  0 <= v < H;   px = floor(u), py = floor(v)
+-ffp-contract=off).  Views are utils.views.View records; the camera coordinates xc, yc, zc and u, v, seen, px, py of a point are
+those of utils/views.py's projection contract.
 
 Mesh.  verts f64 [NV, 3] (any values, NaN included), faces an integer array [F, 3] with 0 <= index < NV; anything else raises
 ValueError.
@@ -63,6 +61,7 @@ import math
 import numpy as np
 
 from utils import carve
+from utils.views import camera, check_count, check_views, image_point, is_cuda, pack, pixel, upload_planes
 
 MAX_VERTS = 1 << 24
 MAX_FACES = 1 << 24
@@ -100,8 +99,7 @@ def _check_knobs(min_cos, depth_tol):
 
 
 def _check_sizes(views):
-    if not 1 <= len(views) <= carve.MAX_VIEWS:
-        raise ValueError(f"{len(views)} views (1 to {carve.MAX_VIEWS})")
+    check_count(len(views))
     for k, v in enumerate(views):
         if int(v.W) < 1 or int(v.H) < 1:
             raise ValueError(f"view {k} ({v.name}): {v.W} x {v.H} pixels")
@@ -116,24 +114,13 @@ def _check_depth(views, depth):
 
 
 # ---- numpy path ------------------------------------------------------------------------------------------------------
-def _camera(view, x, y, z):
-    """(xc, yc, zc): the carving's camera coordinates (carve._project keeps them to itself)."""
-    R, t = view.R, view.t
-    with np.errstate(all="ignore"):
-        xc = ((R[0, 0] * x + R[0, 1] * y) + R[0, 2] * z) + t[0]
-        yc = ((R[1, 0] * x + R[1, 1] * y) + R[1, 2] * z) + t[1]
-        zc = ((R[2, 0] * x + R[2, 1] * y) + R[2, 2] * z) + t[2]
-    return xc, yc, zc
-
-
 def _depth_view(view, verts, faces):
     """(Z f64 [H, W], dropped) of one view.  Every candidate (face, pixel) pair is a row of flat arrays, _CHUNK of them at a time."""
     W, H = int(view.W), int(view.H)
     Z = np.full(H * W, np.inf)
     with np.errstate(all="ignore"):
-        xc, yc, zc = _camera(view, verts[:, 0], verts[:, 1], verts[:, 2])
-        u = view.fx * (xc / zc) + view.cx
-        v = view.fy * (yc / zc) + view.cy
+        xc, yc, zc = camera(view, verts[:, 0], verts[:, 1], verts[:, 2])
+        u, v = image_point(view, xc, yc, zc)
         ok = ((zc > 0.0) & np.isfinite(u) & np.isfinite(v))[faces].all(axis=1)
         f = faces[ok]
         U, Vv, IZ = u[f], v[f], 1.0 / zc[f]
@@ -188,7 +175,7 @@ def _samples(points, normals):
 
 def votes_numpy(points, normals, views, masks, depth, min_cos, depth_tol):
     points, normals = _samples(points, normals)
-    carve._check_views(views, masks)
+    check_views(views, masks)
     _check_depth(views, depth)
     min_cos, depth_tol = _check_knobs(min_cos, depth_tol)
     N = points.shape[0]
@@ -198,9 +185,9 @@ def votes_numpy(points, normals, views, masks, depth, min_cos, depth_tol):
     c2 = min_cos * min_cos
     for k, view in enumerate(views):
         R = view.R
-        seen, py, px = carve._project(view, x, y, z)
+        xc, yc, zc = camera(view, x, y, z)
+        seen, py, px = pixel(view, xc, yc, zc)
         with np.errstate(all="ignore"):
-            xc, yc, zc = _camera(view, x, y, z)
             nc = [(R[r, 0] * n0 + R[r, 1] * n1) + R[r, 2] * n2 for r in range(3)]
             d = -((nc[0] * xc + nc[1] * yc) + nc[2] * zc)
             nn = (nc[0] * nc[0] + nc[1] * nc[1]) + nc[2] * nc[2]
@@ -311,14 +298,14 @@ def _split(depth, records):
 # ---- host-array entry points -----------------------------------------------------------------------------------------
 def depth_maps(verts, faces, views, device=None, budget=None):
     """(maps, dropped): the depth map f64 [H, W] of every view, host arrays, and the number of dropped (face, view) pairs."""
-    if not carve._is_cuda(device):
+    if not is_cuda(device):
         return depth_numpy(verts, faces, views)
     verts, faces = check_mesh(verts, faces)
     _check_sizes(views)
     v_dev, f_dev = _upload_mesh(verts, faces, device)
     maps, dropped = [], 0
     for a, b in view_batches(views, budget):
-        packed = carve.pack(views[a:b], [np.zeros((v.H, v.W), np.uint8) for v in views[a:b]], None, device)
+        packed = pack(views[a:b], [np.zeros((v.H, v.W), np.uint8) for v in views[a:b]], None, device)
         depth, d = depth_device(v_dev, f_dev, packed)
         maps += _split(depth, packed.records)
         dropped += d
@@ -327,18 +314,18 @@ def depth_maps(verts, faces, views, device=None, budget=None):
 
 def scalp_votes(points, normals, views, masks, depth, min_cos, depth_tol, device=None, budget=None):
     """(vis, hits) int32 [N], host arrays; `depth`: the views' maps, host arrays as depth_maps returns them."""
-    if not carve._is_cuda(device):
+    if not is_cuda(device):
         return votes_numpy(points, normals, views, masks, depth, min_cos, depth_tol)
     import torch
     points, normals = _samples(points, normals)
-    carve._check_views(views, masks)
+    check_views(views, masks)
     _check_depth(views, depth)
     p_dev, n_dev = torch.from_numpy(points).to(device), torch.from_numpy(normals).to(device)
     vis = torch.zeros(points.shape[0], dtype=torch.int32, device=device)
     hits = torch.zeros_like(vis)
     for a, b in view_batches(views, budget):
-        packed = carve.pack(views[a:b], masks[a:b], None, device)
-        d_dev = torch.from_numpy(np.concatenate([m.reshape(-1) for m in depth[a:b]])).to(device)
+        packed = pack(views[a:b], masks[a:b], None, device)
+        d_dev = upload_planes(depth[a:b], device)
         v, h = votes_device(p_dev, n_dev, packed, d_dev, min_cos, depth_tol)
         vis += v
         hits += h
@@ -349,10 +336,10 @@ def label_scalp(verts, faces, views, masks, spacing, min_cos, depth_tol, min_vie
     """(scalp_points f64 [n, 3], vis, hits int32 [N], kept bool [N]) over the N samples of surface_samples(verts, faces, spacing).
     `stats`, a dict, receives "dropped": the (face, view) pairs that the depth maps left out."""
     verts, faces = check_mesh(verts, faces)
-    carve._check_views(views, masks)
-    min_views, min_percent = carve._check_rule(min_views, min_percent)
+    check_views(views, masks)
+    min_views, min_percent = carve.check_rule(min_views, min_percent)
     points, normals = surface_samples(verts, faces, spacing)
-    if not carve._is_cuda(device):
+    if not is_cuda(device):
         depth, dropped = depth_numpy(verts, faces, views)
         vis, hits = votes_numpy(points, normals, views, masks, depth, min_cos, depth_tol)
     else:
@@ -363,7 +350,7 @@ def label_scalp(verts, faces, views, masks, spacing, min_cos, depth_tol, min_vie
         hits_dev = torch.zeros_like(vis_dev)
         dropped = 0
         for a, b in view_batches(views, budget):
-            packed = carve.pack(views[a:b], masks[a:b], None, device)
+            packed = pack(views[a:b], masks[a:b], None, device)
             depth, d = depth_device(v_dev, f_dev, packed)
             v, h = votes_device(p_dev, n_dev, packed, depth, min_cos, depth_tol)
             vis_dev += v

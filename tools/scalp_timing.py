@@ -10,14 +10,15 @@ to profiles/scalp_timing.json (--out).
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "hair-gs_amd")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "hair-gs_amd"), os.path.dirname(os.path.abspath(__file__))]
 
 import numpy as np
+
+from carve_timing import events, look_at
 
 W, H, F = 1000, 1000, 1100.0
 AXES = np.array([0.8, 0.9, 1.0])            # the head's half axes
@@ -48,14 +49,6 @@ def icosphere(subdivisions):
     return np.array(verts), np.array(faces, np.int64)
 
 
-def look_at(c):
-    f = -c / np.linalg.norm(c)
-    r = np.cross(f, np.array([0.0, 0.0, 1.0]))
-    r /= np.linalg.norm(r)
-    R = np.stack([r, np.cross(f, r), f])
-    return R, -R @ c
-
-
 def capture(V):
     """(views, masks): a pixel is set iff the ray through its centre first meets the ellipsoid at z > 0.25."""
     from utils.carve import View
@@ -75,21 +68,6 @@ def capture(V):
         z = c[2] + s * (d[..., 2] * AXES[2])
         masks.append(np.where((disc > 0.0) & (s > 0.0) & (z > 0.25), 255, 0).astype(np.uint8))
     return views, masks
-
-
-def events(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts)
 
 
 def main():
