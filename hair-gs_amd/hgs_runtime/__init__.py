@@ -90,6 +90,8 @@ SIGNATURES = {
     "hgs_strand_arclen": (ci, [vp, ci, vp, vp, C.c_longlong, vp, ci, vp, vp, vp]),
     "hgs_strand_resample": (ci, [vp, ci, vp, vp, vp, C.c_longlong, vp, ci, vp, ci, ci, vp, ci, vp, ci, vp, C.c_longlong, vp, vp]),
     "hgs_undistort_images": (ci, [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci]),
+    "hgs_rescale_images": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp, ci]),
+    "hgs_rescale_orientation": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
     "hgs_carve_view_bytes": (sz, []),
     "hgs_carve_votes": (ci, [vp, C.c_longlong, vp, ci, vp, vp, vp, vp, vp, vp]),
     "hgs_carve_grid": (ci, [vp, vp, C.c_double, ci, ci, ci, ci, vp, vp, ci, ci, vp]),

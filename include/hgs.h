@@ -658,6 +658,27 @@ int hgs_strand_resample(void* stream, int S, const long long* offsets, const lon
 int hgs_undistort_images(void* stream, int N, int C, int Hs, int Ws, int Hd, int Wd, int model, const double* src_params_host,
                          const double* dst_pinhole_host, const unsigned char* src, unsigned char* dst, unsigned char* valid, int mode);
 
+/* hgs_rescale_images / hgs_rescale_orientation (csrc/hgs_rescale.hip) <-> the downscaling of a capture (utils/rescale.py states the
+ *   contract, rescale.py is the driver; the reference's parsers write the size they want, and the loader here subsamples the hair
+ *   planes).  Area averaging of [Hs][Ws] planes into [Hd][Wd], 1 <= Wd <= Ws and 1 <= Hd <= Hs, float64, one rounding per operation:
+ *     output column x covers lo = (x*Ws)/Wd to hi = ((x + 1)*Ws)/Wd; i0 = floor(lo); tap k = 0..(Ws + Wd - 1)/Wd reads column
+ *     min(i0 + k, Ws - 1) with wx = min(i0 + k + 1, hi) - max(i0 + k, lo), 0 unless > 0; rows likewise; terms ky outer, kx inner, w = wy*wx.
+ *   hgs_rescale_images: src [N][Hs][Ws][C] uint8 (C = 1, 3 or 4, PIL's layout) -> dst [N][Hd][Wd][C]; per channel acc += w*p, A += w;
+ *     mode 0 (average): min(255, floor(acc/A + 0.5)); mode 1 (threshold, for masks): 255 where acc/A >= 127.5, else 0.
+ *   hgs_rescale_orientation: angle, conf [N][Hs][Ws] uint8 (theta = angle*pi/255, so an orientation is averaged as its double-angle
+ *     vector), mask [N][Hs][Ws] uint8 or NULL (every pixel counts); tables: DEVICE float64 [4][256] built by the host --
+ *     C[t] = cos(2 pi t/255), S[t] = sin(2 pi t/255) (entry 255 = entry 0) and the half-step boundaries HC[j], HS[j] =
+ *     cos, sin(2 pi (j - 0.5)/255), j = 1..255 (entry 0 unused); no trigonometric function is evaluated on the device.  Per term with
+ *     mask != 0: g = w*conf, X += g*C[angle], Y += g*S[angle], Am += w.  conf_out [N][Hd][Wd]: 0 if Am == 0, else
+ *     min(255, floor(sqrt(X*X + Y*Y)/Am + 0.5)).  angle_out: 0 if X == 0 and Y == 0, else (the number of boundaries j that (X, Y) is at
+ *     or past) mod 255, where upper(x, y) = y > 0 or (y == 0 and x > 0) and V is at or past H iff upper(V) != upper(H) and H is the upper
+ *     one, or the halves are equal and HC*Y - HS*X >= 0.
+ *   Bad arguments (N <= 0, sizes <= 0, an output larger than the source, another C or mode, a null buffer other than mask, a plane above
+ *   2^31 - 1 bytes, more than 65535 planes or output rows) return non-zero before anything is launched. */
+int hgs_rescale_images(void* stream, int N, int C, int Hs, int Ws, int Hd, int Wd, const unsigned char* src, unsigned char* dst, int mode);
+int hgs_rescale_orientation(void* stream, int N, int Hs, int Ws, int Hd, int Wd, const unsigned char* angle, const unsigned char* conf,
+                            const unsigned char* mask, const double* tables, unsigned char* angle_out, unsigned char* conf_out);
+
 /* hgs_carve_votes / hgs_carve_grid / hgs_carve_shell (csrc/hgs_carve.hip) <-> the Stage-I point cloud carved from a capture's hair masks
  *   (utils/carve.py states the contract, init_cloud.py is the driver; the reference starts from COLMAP's points or the FLAME vertices).
  *   A view is a PINHOLE camera with its image's pose: R[9] row-major world -> camera, t[3], fx, fy, cx, cy (COLMAP's principal point),
