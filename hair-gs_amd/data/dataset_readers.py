@@ -1,13 +1,15 @@
 """COLMAP scene -> camera infos + point cloud (reference data/dataset_readers.py:34-266).  Images, masks and
 orientation maps are read with PIL (the reference mixes PIL and cv2; cv2 is not in the image):
   <scene>/sparse/0/{cameras,images,points3D}.{bin,txt}   images/<name>   masks/<name>
-  orientations/<stem>_orientation.png (theta = value * pi / 255)   orientations/<stem>_confidence.png (value / 255)"""
+  orientations/<stem>_orientation.png (theta = value * pi / 255)   orientations/<stem>_confidence.png (value / 255)
+The folder and file names are data/capture.py's, which the capture tools share."""
 import os
 from typing import NamedTuple
 
 import numpy as np
 from PIL import Image as PILImage
 
+from data import capture
 from data.colmap import (qvec2rotmat, read_extrinsics_binary, read_extrinsics_text, read_intrinsics_binary,
                          read_intrinsics_text, read_points3D_binary, read_points3D_text)
 from utils.graphics import BasicPointCloud, focal2fov, getWorld2View2
@@ -63,15 +65,14 @@ def readColmapCameras(cam_extrinsics, cam_intrinsics, images_folder, masks_folde
             fx, fy = intr.params[0], intr.params[1]
         else:
             raise AssertionError("Colmap camera model not handled: only undistorted datasets (PINHOLE or SIMPLE_PINHOLE cameras) supported!")
-        fname = os.path.basename(extr.name)
+        fname = capture.file_name(extr)
         image_path = os.path.join(images_folder, fname)
-        stem = fname.split(".")[0]
+        stem = capture.stem(fname)
         mask = field = conf = None
         if masks_folder is not None and os.path.exists(os.path.join(masks_folder, fname)):
             mask = (_gray(os.path.join(masks_folder, fname), w, h, "Mask") / 255.0).astype(bool)   # truncation, as the reference
         if orientations_folder is not None:
-            po = os.path.join(orientations_folder, f"{stem}_orientation.png")
-            pc = os.path.join(orientations_folder, f"{stem}_confidence.png")
+            po, pc = capture.pair_paths(orientations_folder, fname)
             if os.path.exists(po):
                 field = _gray(po, w, h, "Orientation").astype(np.float32) * np.pi / 255.0
             if os.path.exists(pc):
@@ -110,8 +111,8 @@ def readColmapSceneInfo(path, images=None, llffhold=8):
     else:
         extr = read_extrinsics_text(os.path.join(sparse, "images.txt"))
         intr = read_intrinsics_text(os.path.join(sparse, "cameras.txt"))
-    cams = readColmapCameras(extr, intr, os.path.join(path, "images" if images is None else images),
-                             os.path.join(path, "masks"), os.path.join(path, "orientations"))
+    cams = readColmapCameras(extr, intr, os.path.join(path, capture.IMAGES if images is None else images),
+                             os.path.join(path, capture.MASKS), os.path.join(path, capture.ORIENTATIONS))
     cams = sorted(cams, key=lambda c: c.image_name)
     ply_path = os.path.join(sparse, "points3D.ply")
     if not os.path.exists(ply_path):   # converted once, like the reference

@@ -3,7 +3,7 @@
 a `return_table=` keyword the function does not take).  Precision, recall, F1 and strand consistency at the four default
 (distance, angle) pairs, bidirectional like the reference's call, printed as a metrics x thresholds table.
   python eval.py -s <capture with hair_eval_data.npz> -p <point_cloud.ply | model dir> [--device cuda|cpu] [--json out.json]
-A model directory is read at its newest point_cloud/iteration_N.  Only the reference's `-pt gs` loader is provided: a
+A model directory is read at its newest point_cloud/iteration_N (utils/system.py model_ply).  Only the reference's `-pt gs` loader is provided: a
 1-element PLY is a Gaussian cloud (foreground means + longest axes), a 5-element PLY a strand model (its joints in strand
 order); reference data/eval_data.py:174-186."""
 import json
@@ -14,17 +14,6 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from argparse import ArgumentParser
 
 import numpy as np
-
-
-def model_ply(path):
-    """The PLY itself, or <dir>/point_cloud/iteration_<newest>/point_cloud.ply of a model directory."""
-    if os.path.isfile(path):
-        return path
-    pc = os.path.join(path, "point_cloud")
-    its = [int(d.split("_")[-1]) for d in os.listdir(pc) if d.startswith("iteration_")] if os.path.isdir(pc) else []
-    if not its:
-        raise FileNotFoundError(f"{path}: neither a PLY file nor a model directory with point_cloud/iteration_N")
-    return os.path.join(pc, f"iteration_{max(its)}", "point_cloud.ply")
 
 
 def load_eval_data_from_gaussians(path, device="cpu"):
@@ -66,6 +55,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     from data.eval_data import load_hair_eval_data_npz
     from loss.metrics import compute_metrics
+    from utils.system import model_ply
     gt_path = os.path.join(args.source_data_path, "hair_eval_data.npz")
     gt = load_hair_eval_data_npz(gt_path)
     print(f"Loaded GT data from {gt_path}")

@@ -4,7 +4,7 @@ merge.py that the reference leaves to scripts/convert_output.py (MeshLab PLYs of
   python export_strands.py -m <model dir | strand PLY> [-s <capture>] -o <out> --format hair|usc|ply_edges|ply_faces|npz [--format ...]
                            [--points 100] [--min_segments 1] [--min_length 0] [--max_root_distance D] [--colour model|strand]
                            [--device cuda|cpu]
-A model directory is read at its newest point_cloud/iteration_N (eval.py's rule); the SH degree is read off the file.  Every
+A model directory is read at its newest point_cloud/iteration_N (utils/system.py model_ply, as eval.py reads it); the SH degree is read off the file.  Every
 strand is resampled by arc length to --points points (0: its joints as they are) with per-point colour, opacity and width
 (scene/strand_export.py: the contract; --device cuda = the HIP kernels on the model's device tensors, cpu = the numpy path), strands
 with fewer than --min_segments segments, shorter than --min_length or rooted farther than --max_root_distance from the nearest
@@ -83,8 +83,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     formats = list(dict.fromkeys(args.format or ["hair"]))
     from data import strand_files as F
-    from eval import model_ply
     from scene.strand_export import resample_strands
+    from utils.system import model_ply
     ply = model_ply(args.model_path)
     model = load_strand_model(ply, args.source_path, device=args.device)
     print(f"Loaded {ply}: {model.endpoint_pairs.shape[0]} segments, {model.strands_info.n_strands} strands")

@@ -6,7 +6,7 @@ cloud is sparse where hair is and dense on the face, the shoulders and the backg
                        [--images images] [--device cuda|cpu] [--overwrite]
                        [--directions [--orientations orientations] [--rounds 3] [--sigma_deg 10] [--min_conf 1] [--min_coherence 0]]
 Reads <scene>/sparse/0 (binary or text; PINHOLE and SIMPLE_PINHOLE cameras only -- undistort.py makes them), <scene>/masks/<name> for
-every image of the model and, for the hull's colours, <scene>/<images>/<name>.
+every image of the model and, for the hull's colours, <scene>/<images>/<name> (data/capture.py forms the names, as for the loader).
   hull    a --grid voxel grid over the automatic bounds (utils.carve.auto_bounds) or over --bounds is tested against every mask; a voxel
           is kept where at least --min_views views have its centre in frame and --min_percent percent of those see hair there; of the
           kept voxels the shell (a face neighbour empty or outside) is written unless --no_shell.  More than --max_points voxels: those
@@ -38,13 +38,6 @@ import numpy as np
 BACKUPS = ("points3D.colmap.bin", "points3D.colmap.txt")
 
 
-def select(n, max_points):
-    """Positions (ascending) of the kept voxels that are written: all n, or floor(j*n/max_points) for j = 0..max_points - 1."""
-    if n <= max_points:
-        return np.arange(n, dtype=np.int64)
-    return (np.arange(max_points, dtype=np.int64) * n) // max_points
-
-
 def mean_colours(rgb_sum, hits):
     """(sum + hits//2)//hits per channel, 128 where hits == 0; uint8 [n, 3]."""
     hits = np.asarray(hits, np.int64)
@@ -55,10 +48,6 @@ def mean_colours(rgb_sum, hits):
 
 def _fail(msg):
     raise SystemExit(f"init_cloud.py: {msg}")
-
-
-def _stem(view):
-    return os.path.basename(view.name).split(".")[0]             # (the loader's rule, data/dataset_readers.py)
 
 
 def lift_normals(voter, orients, confs, xyz, args):
@@ -135,7 +124,7 @@ def hull_points(voter, args):
     out = occ if args.no_shell else voter.shell(occ)
     flat = np.flatnonzero(out)
     n_shell = flat.size
-    flat = flat[select(flat.size, args.max_points)]
+    flat = flat[voter.carve.select(flat.size, args.max_points)]
     nx, ny, nz = dims
     xs, ys, zs = voter.carve.centres(origin, h, dims)
     xyz = np.stack([xs[flat % nx], ys[(flat // nx) % ny], zs[flat // (nx * ny)]], axis=1)
@@ -147,6 +136,7 @@ def hull_points(voter, args):
 
 
 def main(argv=None):
+    from data import capture
     parser = ArgumentParser(description="Carve the Stage-I point cloud from a capture's hair masks")
     parser.add_argument("--source_path", "-s", required=True, help="scene directory (sparse/0, masks/, <images>/)")
     parser.add_argument("--mode", default="hull", choices=("hull", "filter", "both"))
@@ -161,7 +151,7 @@ def main(argv=None):
     parser.add_argument("--device", default="cuda", help="cuda: the HIP kernels; cpu: the numpy path")
     parser.add_argument("--overwrite", action="store_true")
     parser.add_argument("--directions", action="store_true", help="also lift hair directions into sparse/0/points3D.ply's normals")
-    parser.add_argument("--orientations", default="orientations", help="folder of the <stem>_orientation.png / _confidence.png maps")
+    parser.add_argument("--orientations", default="orientations", help=f"folder of the <stem>{capture.ORIENTATION} / {capture.CONFIDENCE} maps")
     parser.add_argument("--rounds", type=int, default=3, help="re-weighted rounds after the plain least-squares one")
     parser.add_argument("--sigma_deg", type=float, default=10.0, help="angular scale of the re-weighting")
     parser.add_argument("--min_conf", type=int, default=1, help="smallest confidence byte (0 to 255) that votes")
@@ -178,7 +168,7 @@ def main(argv=None):
         _fail("--rounds >= 0, 0 <= --min_conf <= 255 and 0 < --sigma_deg < 180 expected")
     src = args.source_path
     sparse = os.path.join(src, "sparse", "0")
-    if not os.path.isdir(os.path.join(src, "masks")):
+    if not os.path.isdir(os.path.join(src, capture.MASKS)):
         _fail(f"{src} has no masks/ folder: there is nothing to carve with")
     result = os.path.join(sparse, "points3D.bin")
     backup = next((os.path.join(sparse, b) for b in BACKUPS if os.path.exists(os.path.join(sparse, b))), None)
@@ -192,12 +182,12 @@ def main(argv=None):
     orients = confs = None
     try:
         views = load_views(sparse)
-        masks = [read_plane(os.path.join(src, "masks", os.path.basename(v.name)), v, "the mask") for v in views]
-        imgs = [read_plane(os.path.join(src, args.images, os.path.basename(v.name)), v, "the image", "RGB") for v in views] if need_images else None
+        masks = [read_plane(capture.mask_path(src, capture.file_name(v)), v, "the mask") for v in views]
+        imgs = [read_plane(os.path.join(src, args.images, capture.file_name(v)), v, "the image", "RGB") for v in views] if need_images else None
         if args.directions:
-            folder = os.path.join(src, args.orientations)
-            orients = [read_plane(os.path.join(folder, f"{_stem(v)}_orientation.png"), v, "the orientation map") for v in views]
-            confs = [read_plane(os.path.join(folder, f"{_stem(v)}_confidence.png"), v, "the confidence map") for v in views]
+            pairs = [capture.pair_paths(os.path.join(src, args.orientations), capture.file_name(v)) for v in views]
+            orients = [read_plane(pair[0], v, "the orientation map") for pair, v in zip(pairs, views)]
+            confs = [read_plane(pair[1], v, "the confidence map") for pair, v in zip(pairs, views)]
     except ValueError as e:
         _fail(str(e))
     voter = _Voter(views, masks, imgs, None if args.device == "cpu" else "cuda", args.dilate)

@@ -7,7 +7,7 @@ capture of one's own has neither, but it has a head mesh aligned to the cameras 
                        [--min_views 2] [--min_percent 70] [--dilate 0] [--max_points 20000]
                        [--device cuda|cpu] [--overwrite]
 Reads <scene>/sparse/0 (binary or text; PINHOLE and SIMPLE_PINHOLE cameras only -- undistort.py makes them), <scene>/masks/<name> for
-every image of the model, and the mesh: --mesh, by default <scene>/head_mesh.ply.  An OBJ is read by data.head_data.load_obj
+every image of the model (data/capture.py forms the names, as for the loader), and the mesh: --mesh, by default <scene>/head_mesh.ply.  An OBJ is read by data.head_data.load_obj
 (polygons fanned into triangles), a PLY by utils/ply.py (a `vertex` element with x, y, z and a `face` element whose list property
 holds three indices in every row).
 The samples are the mesh's vertices and, with --spacing > 0, points spread over every face about that far apart.  A sample votes in
@@ -16,7 +16,7 @@ the views that see it: in frame, its normal turned towards the camera by at leas
 units).  It is scalp where at least --min_views views see it and --min_percent percent of them find hair at its pixel.  --dilate r
 widens every mask by r pixels first.  These defaults are knobs, not measured optima: hair that hangs in front of skin votes that
 skin as scalp in the views where it does, and --min_percent is what one turns against it.
-More than --max_points kept samples are thinned to those at positions floor(j*n/max_points) of their order (init_cloud.select).
+More than --max_points kept samples are thinned to those at positions floor(j*n/max_points) of their order (utils.carve.select).
 head_reconstruction_data.npz gets head_verts = the mesh's vertices and scalp_verts = the kept points; it is written under a temporary
 name and renamed into place.  A file that is already there is kept, once, as head_reconstruction_data.orig.npz, and is replaced only
 with --overwrite.  main() returns the number of scalp points and prints the counts: samples, never visible, kept, dropped faces."""
@@ -78,8 +78,8 @@ def main(argv=None):
     parser.add_argument("--device", default="cuda", help="cuda: the HIP kernels; cpu: the numpy path")
     parser.add_argument("--overwrite", action="store_true")
     args = parser.parse_args(argv)
+    from data import capture
     from data.head_reconstruction_data import save_head_reconstruction_data_npz
-    from init_cloud import select
     from utils import carve, scalp
     from utils.views import load_views, read_plane
     if args.device not in ("cuda", "cpu"):
@@ -89,14 +89,14 @@ def main(argv=None):
         _fail("--min_views >= 1, 0 <= --min_percent <= 100, --dilate >= 0, --max_points >= 1, 0 <= --min_cos <= 1, --spacing >= 0 and "
               "--depth_tol >= 0 expected")
     src = args.source_path
-    if not os.path.isdir(os.path.join(src, "masks")):
+    if not os.path.isdir(os.path.join(src, capture.MASKS)):
         _fail(f"{src} has no masks/ folder: there is nothing to label with")
     result, backup = os.path.join(src, RESULT), os.path.join(src, BACKUP)
     if os.path.exists(result) and not args.overwrite:
         _fail(f"{result} exists: pass --overwrite to replace it (the first file replaced is kept as {BACKUP})")
     try:
         views = load_views(os.path.join(src, "sparse", "0"))
-        masks = [read_plane(os.path.join(src, "masks", os.path.basename(v.name)), v, "the mask", sized="a mask") for v in views]
+        masks = [read_plane(capture.mask_path(src, capture.file_name(v)), v, "the mask", sized="a mask") for v in views]
     except ValueError as e:
         _fail(str(e))
     verts, faces = load_mesh(args.mesh or os.path.join(src, "head_mesh.ply"))
@@ -119,7 +119,7 @@ def main(argv=None):
     if points.shape[0] == 0:
         _fail(f"no sample is scalp under --min_views {args.min_views}, --min_percent {args.min_percent}, --min_cos {args.min_cos}, "
               f"--depth_tol {depth_tol:.6g}, --dilate {args.dilate} (is the mesh aligned to the cameras?)")
-    points = points[select(points.shape[0], args.max_points)]
+    points = points[carve.select(points.shape[0], args.max_points)]
     tmp = os.path.join(src, f"head_reconstruction_data.{os.getpid()}.tmp.npz")     # (np.savez appends .npz to any other ending)
     save_head_reconstruction_data_npz(tmp, head_verts=verts, scalp_verts=points)
     if os.path.exists(result) and not os.path.exists(backup):                     # the first replacement: the old file moves aside, once

@@ -5,7 +5,6 @@ cloud; the result is saved as iteration_<it + rounds + 1> (the reference's loop 
   python merge.py -s <colmap scene> -m <model dir> [--iterations N]"""
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from argparse import ArgumentParser
@@ -14,22 +13,7 @@ import torch
 
 from arguments import GeneralParams, ModelParams, OptimizationParams
 from scene.hair_gaussian_model import HairGaussianModel
-
-
-def merge_rounds(hair_gs, max_rounds, log=print):
-    """compute_endpoint_pair_to_merge -> merge_endpoint_pairs -> compute_strands_info until no candidate is left."""
-    rounds = 0
-    for i in range(1, max_rounds + 1):
-        t0 = time.time()
-        pairs = hair_gs.compute_endpoint_pair_to_merge()
-        if pairs.shape[0] == 0:
-            break
-        hair_gs.merge_endpoint_pairs(pairs)
-        hair_gs.compute_strands_info()
-        rounds = i
-        log(f"[merge {i}] merged {pairs.shape[0]} endpoint pairs in {time.time() - t0:.3f} s; "
-            f"{hair_gs.strands_info.n_strands} strands, {hair_gs.get_xyz.shape[0]} segments")
-    return rounds
+from scene.hair_topology import merge_rounds
 
 
 def main(argv=None):

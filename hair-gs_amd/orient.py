@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Writes the orientation maps a capture needs for training (what the reference's dataset parsers make with
 utils/vision.py estimate_orientation_field): for every image in <scene>/<images>, <scene>/orientations/<stem>_orientation.png
-(theta * 255 / pi) and <stem>_confidence.png (confidence * 255), both truncated to uint8, stem = name.split(".")[0] as
-data/dataset_readers.py forms it.
+(theta * 255 / pi) and <stem>_confidence.png (confidence * 255), both truncated to uint8; data/capture.py (pair_paths) forms the
+names, for this driver as for the loader.
   python orient.py -s <scene> [--images images] [--device cuda|cpu] [--batch 16] [--overwrite]
                    [--kernel_size 31] [--sigma 2] [--lambda_ 3] [--gamma 0.5] [--num_angles 180]
 Images are read with PIL: mode L as it is, RGB through OpenCV's RGB2GRAY weights, RGBA without its alpha; other modes are refused.
@@ -32,12 +32,11 @@ def list_images(folder):
     return sorted(f for f in os.listdir(folder) if os.path.isfile(os.path.join(folder, f)) and os.path.splitext(f)[1].lower() in exts)
 
 
-def write_maps(out_dir, stem, field, conf):
+def write_maps(pair, field, conf):
     from PIL import Image
     from utils.vision import orientation_pngs
-    o, c = orientation_pngs(field, conf)
-    Image.fromarray(o).save(os.path.join(out_dir, f"{stem}_orientation.png"))
-    Image.fromarray(c).save(os.path.join(out_dir, f"{stem}_confidence.png"))
+    for path, plane in zip(pair, orientation_pngs(field, conf)):
+        Image.fromarray(plane).save(path)
 
 
 def main(argv=None):
@@ -53,33 +52,33 @@ def main(argv=None):
     parser.add_argument("--gamma", type=float, default=0.5)
     parser.add_argument("--num_angles", type=int, default=180)
     args = parser.parse_args(argv)
+    from data import capture
     from utils.vision import NoVarianceError, estimate_orientation_field, estimate_orientation_fields
     params = dict(kernel_size=args.kernel_size, sigma=args.sigma, lambda_=args.lambda_, gamma=args.gamma, num_angles=args.num_angles)
     folder = os.path.join(args.source_path, args.images)
-    out_dir = os.path.join(args.source_path, "orientations")
+    out_dir = os.path.join(args.source_path, capture.ORIENTATIONS)
     os.makedirs(out_dir, exist_ok=True)
     todo = []
     for name in list_images(folder):
-        stem = name.split(".")[0]
-        done = all(os.path.exists(os.path.join(out_dir, f"{stem}_{k}.png")) for k in ("orientation", "confidence"))
-        if done and not args.overwrite:
+        pair = capture.pair_paths(out_dir, name)
+        if all(os.path.exists(path) for path in pair) and not args.overwrite:
             continue
-        todo.append((name, stem))
+        todo.append((name, pair))
     print(f"{len(todo)} view(s) to estimate in {folder}")
     if args.device == "cpu":
-        for name, stem in todo:
+        for name, pair in todo:
             gray = read_gray(os.path.join(folder, name))
             try:
                 field, conf = estimate_orientation_field(gray, **params)
             except ValueError as e:
                 raise SystemExit(f"orient.py: {os.path.join(folder, name)}: {e}")
-            write_maps(out_dir, stem, field, conf)
+            write_maps(pair, field, conf)
         return len(todo)
     import torch
     groups = {}
-    for name, stem in todo:
+    for name, pair in todo:
         g = read_gray(os.path.join(folder, name))
-        groups.setdefault(g.shape, []).append((name, stem, g))
+        groups.setdefault(g.shape, []).append((name, pair, g))
     for views in groups.values():
         for b0 in range(0, len(views), max(1, args.batch)):
             chunk = views[b0:b0 + max(1, args.batch)]
@@ -90,8 +89,8 @@ def main(argv=None):
                 raise SystemExit(f"orient.py: {', '.join(os.path.join(folder, chunk[i][0]) for i in e.views)}: no pixel with nonzero "
                                  "orientation variance (a uniform image?): the confidence is undefined")
             field, conf = field.cpu().numpy(), conf.cpu().numpy()
-            for i, (name, stem, _) in enumerate(chunk):
-                write_maps(out_dir, stem, field[i], conf[i])
+            for i, (_, pair, _) in enumerate(chunk):
+                write_maps(pair, field[i], conf[i])
     return len(todo)
 
 

@@ -7,6 +7,7 @@ search is one query (kd-tree on the CPU, hgs_radius_pairs on the GPU, where the 
 first-occurrence rule) and the greedy selections, sequential in the reference, are resolved in vectorised rounds that keep its
 order (compute_endpoint_pair_to_merge)."""
 import os
+import time
 
 import numpy as np
 import torch
@@ -634,3 +635,20 @@ class HairTopologyMixin:
         prune[r1] = True
         prune[r2] = True
         self.prune_segments(prune)
+
+
+# ---- Stage II: the merge loop (merge.py is its driver) ---------------------------------------------------------------
+def merge_rounds(hair_gs, max_rounds, log=print):
+    """compute_endpoint_pair_to_merge -> merge_endpoint_pairs -> compute_strands_info until no candidate is left."""
+    rounds = 0
+    for i in range(1, max_rounds + 1):
+        t0 = time.time()
+        pairs = hair_gs.compute_endpoint_pair_to_merge()
+        if pairs.shape[0] == 0:
+            break
+        hair_gs.merge_endpoint_pairs(pairs)
+        hair_gs.compute_strands_info()
+        rounds = i
+        log(f"[merge {i}] merged {pairs.shape[0]} endpoint pairs in {time.time() - t0:.3f} s; "
+            f"{hair_gs.strands_info.n_strands} strands, {hair_gs.get_xyz.shape[0]} segments")
+    return rounds

@@ -5,7 +5,7 @@
       [--pct_strands 100] [--line_width 1] [--hsv] [--cam_z (0.5 usc / 0.3 cy)] [--cameras 16] [--height 1000] [--width 1000]
       [--use_gt_hair_verts | --use_strand_root_verts] [--device cuda|cpu] [--normals host|device] [--batch 16] [--overwrite]
 Writes <scene>/images/image_<id>.png (the lit head and the hair), masks/image_<id>.png (255 where the render of the black head and
-the hair is not black), orientations/image_<id>_{orientation,confidence}.png (utils.vision, as orient.py writes them),
+the hair is not black), orientations/image_<id>_{orientation,confidence}.png (utils.vision, as orient.py writes them; the paths are data/capture.py's),
 hair_eval_data.npz, head_reconstruction_data.npz and sparse/0/{cameras,images,points3D}.bin.  The models are [black unlit head,
 lit head (ka = kd = 0.5), lit hair], lit from (0, 5, 5) in white; the cameras ring the hair at its mid-height.  On the GPU the
 images, masks and orientation maps of a batch stay on the device until the PNGs are written.  An existing output folder is
@@ -63,10 +63,11 @@ def _save(path, arr):
 
 def render_capture(models, light, ids, views, projs, width, height, device, batch, out):
     """Renders and writes images, masks and orientation maps; returns the dropped primitive count of all renders."""
+    from data import capture
     from scene.mesh_renderer import render_views
     from utils.vision import estimate_orientation_field, estimate_orientation_fields, orientation_pngs
-    dirs = {k: os.path.join(out, k) for k in ("images", "masks", "orientations")}
-    for d in dirs.values():
+    images, orientations = os.path.join(out, capture.IMAGES), os.path.join(out, capture.ORIENTATIONS)
+    for d in (images, os.path.join(out, capture.MASKS), orientations):
         os.makedirs(d, exist_ok=True)
     dropped = 0
     state = {}
@@ -92,11 +93,11 @@ def render_capture(models, light, ids, views, projs, width, height, device, batc
             fc = [estimate_orientation_field(g) for g in gray]
             field, conf = np.stack([f for f, _ in fc]), np.stack([c for _, c in fc])
         for k, cid in enumerate(ids[sl]):
-            _save(os.path.join(dirs["images"], f"image_{cid}.png"), img[k])
-            _save(os.path.join(dirs["masks"], f"image_{cid}.png"), mask[k])
-            o, c = orientation_pngs(field[k], conf[k])
-            _save(os.path.join(dirs["orientations"], f"image_{cid}_orientation.png"), o)
-            _save(os.path.join(dirs["orientations"], f"image_{cid}_confidence.png"), c)
+            name = f"image_{cid}.png"                            # (the name data.colmap.generate_colmap_data gives the view)
+            _save(os.path.join(images, name), img[k])
+            _save(capture.mask_path(out, name), mask[k])
+            for path, plane in zip(capture.pair_paths(orientations, name), orientation_pngs(field[k], conf[k])):
+                _save(path, plane)
     return dropped
 
 

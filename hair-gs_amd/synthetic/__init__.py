@@ -207,7 +207,7 @@ def stage1_cloud(gt_pts, gt_model, extent, device="cuda", seed=1, jitter=0.002, 
 #   stage1_1080p   the Stage-I cloud of c3_capture (200 k Gaussians from jittered midpoints) after `stage1_iters` iterations of the
 #                  reference's Stage-I loop (densification from 500, every 100)
 #   stage3_merged  the Stage-II product of the same capture: Stage I for `stage1_iters` iterations, to_hair_gaussian_model, merge
-#                  rounds to the fixed point (merge.merge_rounds) -- the model Stage III starts from
+#                  rounds to the fixed point (scene.hair_topology.merge_rounds) -- the model Stage III starts from
 PIPELINE_STATES = {"stage1_1080p": ("c3_capture", "cloud"), "stage3_merged": ("c3_capture", "merged"),
                    # BASELINE config 4's Stage I (10^6 Gaussians from jittered midpoints of curly strands): bench.py --workload stage1_c4
                    # --stage1-iters 0 times its first iterations; not a leg of the default bench line
@@ -220,7 +220,7 @@ def build_pipeline_state(name, device="cuda", seed=0, stage1_iters=None, n_views
     densification events in --, 5000 for stage3_merged, the length tools/three_stage.py runs)."""
     import time
     from arguments import OptimizationParams
-    from train import training
+    from scene.training import training
     from utils.general import safe_state
     capture, kind = PIPELINE_STATES[name]
     spec = CAPTURES[capture]
@@ -250,7 +250,7 @@ def build_pipeline_state(name, device="cuda", seed=0, stage1_iters=None, n_views
         log("stage I", info)
     if kind == "cloud":
         return cloud, cams, extent, info
-    from merge import merge_rounds
+    from scene.hair_topology import merge_rounds
     t0 = time.perf_counter()
     hair = cloud.to_hair_gaussian_model()
     n_before = int(hair.strands_info.n_strands)

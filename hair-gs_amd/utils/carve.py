@@ -39,6 +39,9 @@ n_k = max(1, ceil(side_k / h)), origin = lo.  Known limit: a wisp thinner than a
 Mask dilation.  dilate(mask, r) is the (2r+1)^2 maximum filter of the uint8 plane, exact: shifted maxima in numpy, max_pool2d on the
 device (values 0..255 and a maximum: no rounding).  Host plumbing around the kernels, not part of them.
 
+Thinning.  select(n, max_points): which of n kept voxels (init_cloud.py) or scalp samples (init_scalp.py) are written when there are
+more than max_points.
+
 device=None: numpy.  device="cuda": the kernels, on device tensors.  The caller chooses; neither falls back to the other (the
 convention of utils/normals.py and scene/strand_export.py)."""
 import math
@@ -70,6 +73,13 @@ def _check_grid(h, dims, error=ValueError):
 def keep(seen, hits, min_views, min_percent):
     """The keep rule on integer arrays (numpy or torch)."""
     return (seen >= min_views) & (100 * hits >= min_percent * seen)
+
+
+def select(n, max_points):
+    """Positions (ascending) of the kept voxels or samples that are written: all n, or floor(j*n/max_points) for j = 0..max_points - 1."""
+    if n <= max_points:
+        return np.arange(n, dtype=np.int64)
+    return (np.arange(max_points, dtype=np.int64) * n) // max_points
 
 
 # ---- numpy path ------------------------------------------------------------------------------------------------------

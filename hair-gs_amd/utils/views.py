@@ -19,10 +19,10 @@ point (x, y, z) in view k:
 device=None: numpy.  device="cuda": the kernels, on device tensors.  The caller chooses; neither falls back to the other (the
 convention of utils/normals.py and scene/strand_export.py)."""
 import collections
-import os
 
 import numpy as np
 
+from data import capture
 from data.colmap import qvec2rotmat
 
 MAX_VIEWS = 4096
@@ -50,25 +50,19 @@ def check_count(n):
 def load_views(sparse_dir):
     """The Views of a sparse model (binary or text), in its images' order; ValueError for a camera that is no pinhole or a view count
     out of range."""
-    from undistort import read_sparse
-    cameras, images = read_sparse(sparse_dir)
+    cameras, images = capture.read_sparse(sparse_dir)
     views = [view_of(cameras[im.camera_id], im) for im in images.values()]
     check_count(len(views))
     return views
 
 
 def read_plane(path, view, what, mode="L", sized=None):
-    """The uint8 plane of a view read from an image file and converted to `mode` ([H, W] for L, as the loader reads a mask;
-    [H, W, 3] for RGB), writable.  ValueError for a missing file, which `what` names ("the mask"), or a size that is not the camera's
-    (`sized`, by default `what`)."""
-    from PIL import Image
-    if not os.path.exists(path):
-        raise ValueError(f"{path} is missing ({what} of view {view.name})")
-    with Image.open(path) as im:
-        a = np.array(im.convert(mode))                           # (a writable copy: PIL hands out a read-only view)
-    if a.shape[:2] != (view.H, view.W):
-        raise ValueError(f"{path}: {sized or what} of {a.shape[1]} x {a.shape[0]} pixels, its camera has {view.W} x {view.H}")
-    return a
+    """The uint8 plane of a view read by data.capture.read_image (any format) and converted to `mode` ([H, W] for L, as the loader
+    reads a mask; [H, W, 3] for RGB), writable.  ValueError for a missing file, which `what` names ("the mask"), or a size that is not
+    the camera's (`sized`, by default `what`)."""
+    a, _ = capture.read_image(path, (view.W, view.H), sized or what, "its camera", convert=mode, formats=None,
+                              of=f"{what} of view {view.name}")
+    return np.array(a)                                           # (a writable copy: PIL hands out a read-only view)
 
 
 def check_views(views, masks, images=None):

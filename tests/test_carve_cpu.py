@@ -186,9 +186,10 @@ def test_points_writer_equals_the_struct_writer(tmp_path):
 
 def test_max_points_selection_and_colours():
     import init_cloud
-    assert init_cloud.select(5, 5).tolist() == [0, 1, 2, 3, 4] and init_cloud.select(3, 10).tolist() == [0, 1, 2]
+    from utils.carve import select
+    assert select(5, 5).tolist() == [0, 1, 2, 3, 4] and select(3, 10).tolist() == [0, 1, 2]
     for n, m in ((10, 3), (7, 6), (1000, 999), (200001, 200000)):
-        got = init_cloud.select(n, m)
+        got = select(n, m)
         assert got.tolist() == [(j * n) // m for j in range(m)] and len(set(got.tolist())) == m
     rgb = init_cloud.mean_colours(np.array([[10, 11, 12], [0, 0, 0], [255 * 3, 4, 5]]), np.array([4, 0, 3]))
     assert rgb.dtype == np.uint8 and rgb.tolist() == [[3, 3, 3], [128, 128, 128], [255, 1, 2]]

@@ -216,7 +216,7 @@ def test_carved_cloud_starts_stage_one(tmp_path):
     assert np.isfinite(losses).all()
     # the recorded figure
     from PIL import Image as PILImage
-    from undistort import read_sparse
+    from data.capture import read_sparse
     cameras, images = read_sparse(os.path.join(str(src), "sparse", "0"))
     views = [carve.view_of(cameras[im.camera_id], im) for im in images.values()]
     masks = [np.asarray(PILImage.open(os.path.join(str(src), "masks", v.name)).convert("L")) for v in views]

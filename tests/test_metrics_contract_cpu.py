@@ -80,13 +80,14 @@ def test_eval_cli_on_the_cpu_scores_a_saved_strand_model(tmp_path, capsys):
     import eval as eval_cli
     from data.eval_data import load_hair_eval_data_npz
     from loss.metrics import compute_metrics
+    from utils.system import model_ply
     ply = _strand_capture(str(tmp_path / "capture"))
     out = tmp_path / "m.json"
     metrics, labels = eval_cli.main(["-s", str(tmp_path / "capture"), "-p", str(tmp_path / "capture" / "model"), "--device", "cpu",
                                      "--json", str(out)])
     text = capsys.readouterr().out
     assert "precision(b)" in text and "strand_consistency(b)" in text and labels[0] in text
-    assert eval_cli.model_ply(str(tmp_path / "capture" / "model")) == ply
+    assert model_ply(str(tmp_path / "capture" / "model")) == ply
     # the same as scoring the model's own joints by hand
     pred = eval_cli.load_eval_data_from_gaussians(ply, device="cpu")
     want, _ = compute_metrics(pred, load_hair_eval_data_npz(str(tmp_path / "capture" / "hair_eval_data.npz")), bidirectional=True)

@@ -164,11 +164,12 @@ def test_train_eval_device_matches_the_cpu_evaluation_of_the_saved_model(tmp_pat
     from data.eval_data import load_hair_eval_data_npz
     from loss.metrics import compute_metrics
     from tests.test_dataset_io_cpu import _write_capture, _write_side_files
+    from utils.system import model_ply
     src, model = tmp_path / "capture", tmp_path / "out"
     _write_capture(src, n_views=3, W=64, H=48)
     _write_side_files(src)
     scene = train_cli.main(["-s", str(src), "-m", str(model), "--iterations", "4", "--quiet", "--eval_device", "cuda"])
-    pred = eval_cli.load_eval_data_from_gaussians(eval_cli.model_ply(str(model)), device="cuda")
+    pred = eval_cli.load_eval_data_from_gaussians(model_ply(str(model)), device="cuda")
     want, labels = compute_metrics(pred, load_hair_eval_data_npz(str(src / "hair_eval_data.npz")), bidirectional=True)   # (bidirectional_eval)
     assert scene.eval_thresholds == labels
     _same(want, scene.eval_metrics)
