@@ -77,6 +77,9 @@ class OptimizationParams(ParamGroup):
         # the magnet term (lambda_magnet > 0) as a device op inside the fused, captured iteration (hgs_runtime.fused.magnet_loss)
         # instead of the op-by-op single-pass iteration
         ("fused_magnet", False, False),
+        # the head-penetration term of a strand model (utils/head_sdf.py; off by default): its weight, and how far outside the head's
+        # surface, in scene units, a joint already pays.  train.py loads <source_path>/head_sdf.npz (head_sdf.py writes it)
+        ("lambda_head", 0.0, False), ("head_margin", 0.0, False),
     )
 
     def _finalise(self):

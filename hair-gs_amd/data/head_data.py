@@ -44,6 +44,30 @@ def load_obj(path):
     return v, f, np.array(normals, dtype=np.float32).reshape(-1, 3)
 
 
+def load_mesh(path):
+    """(verts f64 [NV, 3], faces int64 [F, 3]) of a capture's head mesh, an OBJ or a triangle PLY (a `vertex` element with x, y, z and
+    a `face` element whose list property holds three indices in every row); ValueError otherwise.  The drivers that read
+    <scene>/head_mesh.ply (init_scalp.py, head_sdf.py) go through here and refuse in their own names."""
+    import os
+    if not os.path.exists(path):
+        raise ValueError(f"{path} is missing (the head mesh; --mesh names another)")
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".obj":
+        verts, faces, _ = load_obj(path)
+        return verts.astype(np.float64), faces
+    if ext == ".ply":
+        from utils.ply import read_ply
+        els = dict(read_ply(path))
+        if "vertex" not in els or "face" not in els or not all(n in els["vertex"].dtype.names for n in "xyz"):
+            raise ValueError(f"{path}: a vertex element with x, y, z and a face element expected")
+        vertex, face = els["vertex"], els["face"]
+        lists = [n for n in face.dtype.names if face.dtype[n].shape]
+        if len(lists) != 1 or face.dtype[lists[0]].shape != (3,):
+            raise ValueError(f"{path}: faces of three vertices each expected (a triangle mesh)")
+        return np.stack([vertex[n].astype(np.float64) for n in "xyz"], axis=1), face[lists[0]].astype(np.int64)
+    raise ValueError(f"{path}: an .obj or a .ply mesh expected")
+
+
 def _vertex_normals(verts, faces, normals, normals_device=None):
     if normals.shape[0] == faces.shape[0]:
         out = np.zeros((verts.shape[0], 3))

@@ -100,6 +100,10 @@ SIGNATURES = {
     "hgs_lift_solve": (ci, [vp, C.c_longlong, vp, vp, ci, vp, vp]),
     "hgs_scalp_depth": (ci, [vp, ci, vp, ci, vp, ci, vp, vp, vp]),
     "hgs_scalp_votes": (ci, [vp, C.c_longlong, vp, vp, ci, vp, vp, vp, C.c_double, C.c_double, vp, vp]),
+    "hgs_mesh_sdf": (ci, [vp, ci, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, vp, vp]),
+    "hgs_head_penalty_num_blocks": (ci, [ci]),
+    "hgs_head_penalty_forward": (ci, [vp, ci, vp, vp, ci, ci, ci, cf, cf, cf, cf, cf, vp, vp, vp, vp, vp]),
+    "hgs_head_penalty_backward": (ci, [vp, ci, vp, vp, vp]),
     "hgs_oriented_match_scratch_bytes": (sz, [ci]),
     "hgs_oriented_match": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, sz]),
     "hgs_strand_votes": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]),

@@ -1,5 +1,5 @@
 """torch.autograd front-ends of the fused HIP kernels that replace PyTorch-side chains on the training-step path
-(include/hgs.h: hgs_strand_geometry_*, hgs_ssim_l1_*, hgs_orientation_loss_*, hgs_magnet_*).  GPU tensors only."""
+(include/hgs.h: hgs_strand_geometry_*, hgs_ssim_l1_*, hgs_orientation_loss_*, hgs_magnet_*, hgs_head_penalty_*).  GPU tensors only."""
 import ctypes as C
 import math
 
@@ -276,6 +276,67 @@ def set_magnet_search(mode):
     """The neighbour search of magnet_loss, process-wide: None / -1 automatic (by the number of ends), 0 tiles, 1 grid.  Returns
     the previous mode.  A test and A/B switch: both paths give identical bits."""
     return rt.lib().hgs_set_magnet_search(-1 if mode is None else int(mode))
+
+
+class HeadScratch:
+    """What head_penalty keeps between its forward and its backward for E points: g [E, 3], pen and dist [E] (float32) and the
+    forward's float64 partial sums.  The fused iteration holds one for the model's E and replaces it in refresh() after a topology
+    event; a call without one allocates its own."""
+
+    def __init__(self, E, device):
+        E = int(E)
+        f32 = dict(dtype=torch.float32, device=device)
+        self.E = E
+        self.g = torch.empty((E, 3), **f32)
+        self.pen, self.dist = torch.empty((E,), **f32), torch.empty((E,), **f32)
+        self.partials = torch.empty((max(1, int(rt.lib().hgs_head_penalty_num_blocks(E))),), dtype=torch.float64, device=device)
+
+
+class _HeadPenalty(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, sdf, margin, info, scratch):
+        points = rt.require_gpu_tensor(points, "points", torch.float32)
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise rt.HgsError(f"head_penalty: points {tuple(points.shape)}: [E, 3] expected")
+        E, dev = int(points.shape[0]), points.device
+        if scratch is None:
+            scratch = HeadScratch(E, dev)
+        elif scratch.E != E or scratch.g.device != dev:
+            raise rt.HgsError(f"head_penalty: the scratch was made for {scratch.E} points on {scratch.g.device}, the call has {E} on "
+                              f"{dev}: a topology event needs a new one (FusedStrandStep.refresh())")
+        field = sdf.on(dev)
+        phi = field["phi"]
+        nx, ny, nz = sdf.shape
+        if phi.numel() != nx * ny * nz:
+            raise rt.HgsError(f"head_penalty: a field of {phi.numel()} values for a grid of {nx} x {ny} x {nz} nodes")
+        out = torch.empty((1,), dtype=torch.float32, device=dev)
+        o = sdf.origin32
+        with torch.cuda.device(dev):
+            rt.check(rt.lib().hgs_head_penalty_forward(rt.current_stream(), E, rt.ptr(points), rt.ptr(phi), nx, ny, nz, float(o[0]),
+                                                       float(o[1]), float(o[2]), float(sdf.inv_h32), float(margin), rt.ptr(scratch.g),
+                                                       rt.ptr(scratch.pen), rt.ptr(scratch.dist), rt.ptr(scratch.partials), rt.ptr(out)))
+        ctx.scratch, ctx.E = scratch, E
+        if info is not None:
+            info.update(out=out, pen=scratch.pen, dist=scratch.dist, g=scratch.g)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, go):
+        scratch, E = ctx.scratch, ctx.E
+        go = go.contiguous().to(torch.float32)
+        d = torch.empty_like(scratch.g)
+        with torch.cuda.device(d.device):
+            rt.check(rt.lib().hgs_head_penalty_backward(rt.current_stream(), E, rt.ptr(scratch.g), rt.ptr(go), rt.ptr(d)))
+        return d, None, None, None, None
+
+
+def head_penalty(points, sdf, margin, info=None, scratch=None):
+    """The head-penetration term (utils/head_sdf.py states it; loss.losses.head_penetration_loss is the same statement in torch ops)
+    of `points` [E, 3] against the HeadSDF `sdf` as one device op: the scalar, differentiable w.r.t. points, no host synchronisation.
+    `info`: a dict that receives the op's other outputs (device tensors, no copy): "out" ([1]: the value), "pen" and "dist" ([E]: the
+    per-point penalty and interpolated distance, +inf out of range), "g" ([E, 3]: the gradient for an upstream of E).  `scratch`: a
+    HeadScratch for E points that the call works in (and that the next call overwrites); None: its own."""
+    return _HeadPenalty.apply(points, sdf, margin, info, scratch)
 
 
 class FusedAdam(torch.optim.Optimizer):

@@ -318,7 +318,9 @@ def _raster_head_forward(step, xyz, scale, quat, opacity, extra4, shs, endpoints
         d_extra.fill_(float("nan"))
     # the tail of the head's reduction rides in the backward's parameter launch (include/hgs.h HgsHeadTail)
     # (with the magnet term loss() adds to the head's total right after this forward: the total must be complete by then)
-    hp.defer_tail = 1 if (step.defer_tail and xyz.shape[0] > 0 and getattr(step, "magnet", None) is None) else 0
+    # (the same with the head-penetration term)
+    hp.defer_tail = 1 if (step.defer_tail and xyz.shape[0] > 0 and getattr(step, "magnet", None) is None
+                          and getattr(step, "head_sdf", None) is None) else 0
     with torch.cuda.device(dev):
         rt.check(L.hgs_loss_head_forward(rt.current_stream(), C.byref(hp), planes[0:3].data_ptr(), planes[3].data_ptr(),
                                          planes[4:7].data_ptr(), vt.slot.data_ptr(), rt.ptr(endpoints), rt.ptr(smooth_idx),
@@ -584,6 +586,8 @@ class FusedStrandStep:
         self.last = {}
         # the magnet term's topology table (hgs_runtime.fused.MagnetTable) when the term runs inside this iteration, else None
         self.magnet = None
+        # the head's distance field (utils.head_sdf.HeadSDF) when the head-penetration term runs inside this iteration, else None
+        self.head_sdf = None
         self.refresh()
 
     def inline_adam_possible(self):
@@ -591,11 +595,12 @@ class FusedStrandStep:
         rasterizer's (hgs_backward_multi_params; a strand model also needs the endpoint adjacency), a FusedAdam that holds
         exactly the in-lane tensors (higher SH coefficients would need a launch of their own) -- and not switched off.  Not with
         the magnet term: the endpoints' gradient then has a second contributor (autograd adds the two), so the update cannot
-        run in the gather's lanes and Adam's own launch returns."""
+        run in the gather's lanes and Adam's own launch returns.  The head-penetration term is such a contributor too."""
         from hgs_runtime.fused import FusedAdam
         g = self.gaussians
-        return (self.magnet is None and self.fuse_param_backward and isinstance(getattr(g, "optimizer", None), FusedAdam)
-                and g._features_rest.numel() == 0 and getattr(self, "ep_segments", True) is not None
+        return (self.magnet is None and self.head_sdf is None and self.fuse_param_backward
+                and isinstance(getattr(g, "optimizer", None), FusedAdam) and g._features_rest.numel() == 0
+                and getattr(self, "ep_segments", True) is not None
                 and bool(getattr(self.opt, "inline_adam", True)) and os.environ.get("HGS_INLINE_ADAM", "1") != "0"
                 and not (torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1))
 
@@ -631,6 +636,14 @@ class FusedStrandStep:
         if self.lambda_magnet > 0 and bool(getattr(self.opt, "fused_magnet", False)):
             from hgs_runtime.fused import MagnetTable
             self.magnet = MagnetTable.of(g)
+        # the head-penetration term inside the iteration (opt.lambda_head > 0 and a field on the model): its scratch follows E
+        self.lambda_head = float(getattr(self.opt, "lambda_head", 0.0))
+        self.head_sdf = self.head_scratch = None
+        if self.lambda_head > 0 and getattr(g, "head_sdf", None) is not None:
+            from hgs_runtime.fused import HeadScratch
+            self.head_sdf, self.head_margin = g.head_sdf, float(getattr(self.opt, "head_margin", 0.0))
+            self.head_sdf.on(g._endpoints.device)      # (the field's device copy: made here, not inside a capture)
+            self.head_scratch = HeadScratch(g._endpoints.shape[0], g._endpoints.device)
         # endpoint adjacency for the gather-mode backward (HgsStrandFusion.ep_segments / ep_pairs): an endpoint of a
         # chain touches <= 2 segments and <= 4 smoothness-pair roles; anything denser keeps the scatter (atomic) mode.
         # Remembered on the model for as long as both index tables are the same tensors (a topology event assigns new ones): the
@@ -661,6 +674,12 @@ class FusedStrandStep:
             m = magnet_loss(g._endpoints, self.magnet, g.min_val)
             self.last["magnet"] = m.detach()
             loss = loss + self.lambda_magnet * m
+        if self.head_sdf is not None:
+            # loss + lambda_head * term, as loss_function_single_pass adds it: a further autograd node, added the way the magnet's is
+            from hgs_runtime.fused import head_penalty
+            hd = head_penalty(g._endpoints, self.head_sdf, self.head_margin, None, self.head_scratch)
+            self.last["head"] = hd.detach()
+            loss = loss + self.lambda_head * hd
         return loss, terms
 
     def backward(self, loss):
@@ -672,6 +691,8 @@ class FusedStrandStep:
         d = {k: t[i] for i, k in enumerate(rt.HEAD_OUT[1:6], start=1)}
         if "magnet" in self.last:
             d["magnet"] = self.last["magnet"]
+        if "head" in self.last:
+            d["head"] = self.last["head"]
         return d
 
     def update_densification_stats(self):
@@ -763,6 +784,7 @@ class FusedCloudStep(FusedStrandStep):
         g = self.gaussians
         self.smooth_pairs = None
         self.magnet = None          # (a Gaussian cloud has no strand ends)
+        self.head_sdf = None        # (nor joints to keep out of the head: as with smoothness, Stage I has no such term)
         self.head = head_params(self.views.H, self.views.W, self.opt, 0, 0, getattr(g, "min_val", 1e-7),
                                 self.views.has_float_mask)
 

@@ -36,31 +36,12 @@ def _fail(msg):
 
 
 def load_mesh(path):
-    """(verts f64 [NV, 3], faces int64 [F, 3]) of an OBJ or a triangle PLY."""
-    if not os.path.exists(path):
-        _fail(f"{path} is missing (the head mesh; --mesh names another)")
-    ext = os.path.splitext(path)[1].lower()
-    if ext == ".obj":
-        from data.head_data import load_obj
-        try:
-            verts, faces, _ = load_obj(path)
-        except ValueError as e:
-            _fail(str(e))
-        return verts.astype(np.float64), faces
-    if ext == ".ply":
-        from utils.ply import read_ply
-        try:
-            els = dict(read_ply(path))
-        except ValueError as e:
-            _fail(str(e))
-        if "vertex" not in els or "face" not in els or not all(n in els["vertex"].dtype.names for n in "xyz"):
-            _fail(f"{path}: a vertex element with x, y, z and a face element expected")
-        vertex, face = els["vertex"], els["face"]
-        lists = [n for n in face.dtype.names if face.dtype[n].shape]
-        if len(lists) != 1 or face.dtype[lists[0]].shape != (3,):
-            _fail(f"{path}: faces of three vertices each expected (a triangle mesh)")
-        return np.stack([vertex[n].astype(np.float64) for n in "xyz"], axis=1), face[lists[0]].astype(np.int64)
-    _fail(f"{path}: an .obj or a .ply mesh expected")
+    """(verts f64 [NV, 3], faces int64 [F, 3]) of an OBJ or a triangle PLY (data.head_data.load_mesh; refused in this driver's name)."""
+    from data import head_data
+    try:
+        return head_data.load_mesh(path)
+    except ValueError as e:
+        _fail(str(e))
 
 
 def main(argv=None):

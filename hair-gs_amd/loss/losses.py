@@ -170,6 +170,40 @@ def strand_joints_magnet_loss(gaussians: HairGaussianModel):
     return torch.mean(sq * sq)
 
 
+def head_penetration_loss(gaussians: HairGaussianModel, sdf, margin):
+    """Keeps the strand joints out of the head (this package's own term, enabled by --lambda_head, 0 by default; the reference has
+    none): the mean over ALL joints of (margin - d)^2 where the joint lies inside the box of the head's distance field `sdf` (a
+    utils.head_sdf.HeadSDF) and its trilinearly interpolated distance d is below `margin`.  utils/head_sdf.py states the arithmetic;
+    this is the same statement in torch ops, in the same order -- index arithmetic, where and gathers, no selection on the host, so it
+    can be captured and it runs on a CPU model; hgs_runtime.fused.head_penalty is the device op."""
+    p = gaussians._endpoints
+    E = p.shape[0]
+    if E == 0:
+        return p.sum() * 0.0
+    field = sdf.on(p.device)
+    phi = field["phi"]
+    nx, ny, nz = sdf.shape
+    t = (p - field["origin"]) * field["inv_h"]
+    ok = (torch.isfinite(t) & (t >= 0) & (t < field["top"])).all(dim=1)
+    t = torch.where(ok[:, None], t, torch.zeros_like(t))
+    fl = torch.floor(t.detach())
+    f = t - fl
+    i = fl.long()
+    ix, iy, iz = i[:, 0], i[:, 1], i[:, 2]
+    jx, jy, jz = (ix + 1).clamp(max=nx - 1), (iy + 1).clamp(max=ny - 1), (iz + 1).clamp(max=nz - 1)   # (rows out of range: any valid address)
+    c = {(x, y, z): phi[((jz if z else iz) * ny + (jy if y else iy)) * nx + (jx if x else ix)] for x in (0, 1) for y in (0, 1) for z in (0, 1)}
+    fx, fy, fz = f[:, 0], f[:, 1], f[:, 2]
+
+    def lerp(u, v, w):
+        return u + w * (v - u)
+    c00, c10 = lerp(c[0, 0, 0], c[1, 0, 0], fx), lerp(c[0, 1, 0], c[1, 1, 0], fx)
+    c01, c11 = lerp(c[0, 0, 1], c[1, 0, 1], fx), lerp(c[0, 1, 1], c[1, 1, 1], fx)
+    d = lerp(lerp(c00, c10, fy), lerp(c01, c11, fy), fz)
+    r = margin - d
+    pen = torch.where(ok & (r > 0), r * r, torch.zeros_like(r))
+    return pen.sum() / E
+
+
 _BLACK = {}
 _BG_HOST = {}
 
@@ -279,6 +313,9 @@ def loss_function_single_pass(gaussians, viewpoint_cam, args, bg, black_backgrou
         if args.lambda_magnet > 0:
             terms["magnet"] = strand_joints_magnet_loss(gaussians)
             loss = loss + args.lambda_magnet * terms["magnet"]
+        if getattr(args, "lambda_head", 0.0) > 0 and getattr(gaussians, "head_sdf", None) is not None:
+            terms["head"] = head_penetration_loss(gaussians, gaussians.head_sdf, getattr(args, "head_margin", 0.0))
+            loss = loss + args.lambda_head * terms["head"]
     return loss, terms, pkg
 
 
@@ -305,4 +342,7 @@ def loss_function(gaussians, image, viewpoint_cam, args):
         if args.lambda_magnet > 0:
             terms["magnet"] = strand_joints_magnet_loss(gaussians)
             loss = loss + args.lambda_magnet * terms["magnet"]
+        if getattr(args, "lambda_head", 0.0) > 0 and getattr(gaussians, "head_sdf", None) is not None:
+            terms["head"] = head_penetration_loss(gaussians, gaussians.head_sdf, getattr(args, "head_margin", 0.0))
+            loss = loss + args.lambda_head * terms["head"]
     return loss, terms

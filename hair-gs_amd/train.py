@@ -14,7 +14,9 @@ def main(argv=None):
     """Command-line driver (reference train.py:38-131, 256-265 without logger / viewer / evaluation):
       python train.py -s <colmap scene> -m <model dir> [--iterations N] [--save_frequency K]
     Resumes from the newest <model dir>/point_cloud/iteration_*/point_cloud.ply (Gaussian cloud = Stage I, strand model =
-    Stage III) or starts Stage I from the sparse COLMAP points; saves every save_frequency iterations and at the end."""
+    Stage III) or starts Stage I from the sparse COLMAP points; saves every save_frequency iterations and at the end.
+    --lambda_head L (this package's own, off by default) adds the head-penetration term to a strand model's loss; it needs
+    <scene>/head_sdf.npz, which head_sdf.py builds (utils/head_sdf.py)."""
     from argparse import ArgumentParser
     from arguments import GeneralParams, ModelParams, OptimizationParams
     from scene import Scene
@@ -22,6 +24,18 @@ def main(argv=None):
     parser = ArgumentParser(description="Training script parameters")
     mp, op, gp = ModelParams(parser), OptimizationParams(parser), GeneralParams(parser)
     args = parser.parse_args(argv)
+    head_sdf = None
+    if float(args.lambda_head) > 0:
+        # the head-penetration term needs the head's distance field: looked for before anything is loaded or written
+        from utils.head_sdf import load_sdf, scene_sdf_path
+        path = scene_sdf_path(os.path.abspath(args.source_path))
+        if not os.path.exists(path):
+            raise SystemExit(f"train.py: --lambda_head {args.lambda_head} needs {path}: head_sdf.py -s <scene> builds it from the "
+                             "capture's head mesh")
+        try:
+            head_sdf = load_sdf(path)
+        except ValueError as e:
+            raise SystemExit(f"train.py: {e}") from None
     # view-parallel run (python -m torch.distributed.run ... train.py): one process per GPU, initialised before anything
     # touches the GPU; every rank seeds identically (replicated topology operators draw the same random numbers), rank 0
     # alone writes to the model directory
@@ -52,6 +66,8 @@ def main(argv=None):
         dist.barrier()
     opt = op.extract(args)
     g = scene.gaussians
+    if head_sdf is not None:
+        g.head_sdf = head_sdf    # rides on the model: loss/losses.py and hgs_runtime/strand_step.py read gaussians.head_sdf
     g.training_setup(opt)
     cams = scene.getCameras()
     vp = ViewParallel()

@@ -844,6 +844,26 @@ int hgs_raster_resolve(void* stream, int V, int W, int H, int n_models, const Hg
                        const unsigned char* background_host, const int* tile_counts, const long long* tile_offsets,
                        const unsigned* list, unsigned char* rgb, unsigned char* gray);
 
+/* The head mesh as a signed distance field and the penetration term that samples it (csrc/hgs_sdf.hip; utils/head_sdf.py states
+ *   the contract and has the numpy path).  Every argument is checked before a pointer is touched.
+ * hgs_mesh_sdf: tris [F][9] float64 (device): v0, v1, v2 of every face, all finite (the caller drops the others).  Node (ix, iy, iz)
+ *   of the grid lies at origin + index * h; phi [nz][ny][nx] float32 receives +-sqrt(min over the faces of the squared point-triangle
+ *   distance), negative where the generalized winding number exceeds 0.5, a zero as +0; winding (nullable) [nz][ny][nx] float64
+ *   receives that number.  Float64, one rounding per operation; |phi| does not depend on the faces' order.  1 <= F <= 2^24, 1 <= n <=
+ *   1024 an axis.
+ * hgs_head_penalty_forward: points [E][3] float32, phi as above, origin and 1/h rounded to float32.  Per point, in float32:
+ *   t = (p - origin) * inv_h; in range iff 0 <= t < n - 1 on every axis (a NaN is not); d = the trilinear interpolant (x, then y,
+ *   then z), r = margin - d; pen = r r and g = (-2 r) grad d where in range and r > 0, else 0.  g [E][3] (scratch the backward reads),
+ *   pen [E] and dist [E] (both nullable; dist = d, +inf out of range), partials: hgs_head_penalty_num_blocks(E) doubles of scratch,
+ *   out [1] = float(sum of pen in float64 / E), 0 for E = 0.  Two launches, bitwise reproducible, no atomics.
+ * hgs_head_penalty_backward: d_points [E][3] = g * (upstream[0] / float(E)), upstream in device memory.  One launch. */
+int hgs_mesh_sdf(void* stream, int F, const double* tris, double ox, double oy, double oz, double h, int nx, int ny, int nz, float* phi,
+                 double* winding);
+int hgs_head_penalty_num_blocks(int E);
+int hgs_head_penalty_forward(void* stream, int E, const float* points, const float* phi, int nx, int ny, int nz, float ox, float oy,
+                             float oz, float inv_h, float margin, float* g, float* pen, float* dist, double* partials, float* out);
+int hgs_head_penalty_backward(void* stream, int E, const float* g, const float* upstream, float* d_points);
+
 /* Tuning knob of the segment-parallel blend (csrc/hgs_blend.hip): tile lists longer than 1.5 segment lengths are walked
  * by one workgroup per segment (the forward walks a list of exactly two segments with one workgroup); the segment length of a pass with R instances is R / target_segments rounded up to a
  * multiple of 64 and clamped to [min_len, max_len] (multiples of 64, min_len >= 128; default 128, 1024, 2048).  Process-wide, takes
