@@ -104,6 +104,10 @@ SIGNATURES = {
     "hgs_head_penalty_num_blocks": (ci, [ci]),
     "hgs_head_penalty_forward": (ci, [vp, ci, vp, vp, ci, ci, ci, cf, cf, cf, cf, cf, vp, vp, vp, vp, vp]),
     "hgs_head_penalty_backward": (ci, [vp, ci, vp, vp, vp]),
+    "hgs_field_splat": (ci, [vp, ci, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, C.c_double, vp, vp]),
+    "hgs_field_solve": (ci, [vp, ci, ci, ci, vp, vp, vp]),
+    "hgs_strand_trace": (ci, [vp, ci, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, C.c_double, ci,
+                              C.c_double, C.c_double, ci, vp, vp, vp]),
     "hgs_oriented_match_scratch_bytes": (sz, [ci]),
     "hgs_oriented_match": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, sz]),
     "hgs_strand_votes": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]),
@@ -387,6 +391,24 @@ def scalp_check(records, views_dev, masks, depth, faces=None, n_verts=None):
         if faces.numel() and (int(faces.min()) < 0 or int(faces.max()) >= int(n_verts)):
             raise HgsError(f"a face index is out of range of the {n_verts} vertices")
     return len(planes)
+
+
+def trace_check(acc=None, shape=None, skipped=None, dir=None, conf=None):
+    """What the hgs_field_* / hgs_strand_trace kernels trust beyond their own argument checks: the node arrays they index by the grid's
+    shape are contiguous device tensors of exactly that many nodes."""
+    import torch
+    nx, ny, nz = (int(n) for n in shape)
+    if min(nx, ny, nz) < 2 or max(nx, ny, nz) > 1024 or nx * ny * nz > (1 << 26):
+        raise HgsError(f"a grid of {nx} x {ny} x {nz} nodes (2 to 1024 an axis, at most 2^26 in all)")
+    nodes = nx * ny * nz
+    for t, name, dtype, per in ((acc, "acc", torch.int64, 7), (skipped, "skipped", torch.int32, None), (dir, "dir", torch.float64, 3),
+                                (conf, "conf", torch.float64, 1)):
+        if t is None:
+            continue
+        require_device_buffer(t, name, dtype)
+        want = 1 if per is None else nodes * per
+        if t.numel() != want:
+            raise HgsError(f"{name} holds {t.numel()} values, a grid of {nx} x {ny} x {nz} nodes takes {want}")
 
 
 KERNEL_COUNT = 18

@@ -864,6 +864,28 @@ int hgs_head_penalty_forward(void* stream, int E, const float* points, const flo
                              float oz, float inv_h, float margin, float* g, float* pen, float* dist, double* partials, float* out);
 int hgs_head_penalty_backward(void* stream, int E, const float* g, const float* upstream, float* d_points);
 
+/* Strands traced from the scalp through the lifted hair directions (csrc/hgs_trace.hip; utils/trace.py states the contract and has
+ *   the numpy paths).  All float64, one rounding per operation.  Every argument is checked before a pointer is touched.  The grid:
+ *   node (ix, iy, iz) lies at origin + index * h, 2 <= n <= 1024 an axis, at most 2^26 nodes in all.
+ * hgs_field_splat: points, dirs [N][3] float64 (device), 0 <= N <= 2^24.  A point that is not finite, or whose dot(dir, dir) is not
+ *   finite or not > 0, adds one to skipped[0] and nothing else.  The others, with d = dir / sqrt(dot(dir, dir)), add to every node
+ *   with d2 = |node - point|^2 < r2, for k = 1 - d2 / r2: rint(k * 2^32) to the node's W and rint((k * (d_a * d_b)) * 2^32) to its
+ *   xx, xy, xz, yy, yz, zz.  acc [nz][ny][nx][7] int64 (W, xx, xy, xz, yy, yz, zz) and skipped [1] int32 are ADDED to: the caller
+ *   zeroes them, and may splat a cloud in parts.  64-bit integer atomics: the sums are exact, the same bits in any order.
+ *   sqrt(r2) <= 8 h.
+ * hgs_field_solve: per node, T = Tq * 2^-32; dir [nz][ny][nx][3] = the unit eigenvector of the largest eigenvalue l2, its component
+ *   of largest magnitude positive (lowest index on a tie); conf [nz][ny][nx] = l2 - l1; both 0 where W == 0.  Cyclic Jacobi.
+ * hgs_strand_trace: roots, p0 [S][3] float64, 0 <= S <= 2^24; dir, conf as above.  One lane per root walks utils/trace.py's loop:
+ *   at most max_steps (1 to 4096) steps of length `step` through the field interpolated at t = (x - origin) * (1 / h), the range test
+ *   0 <= t < n - 1 in front of every load.  joints [S][max_steps + 1][3] (rows from count on are unspecified), count [S] int32,
+ *   reason [S] int32: 0 steps, 1 bounds, 2 turn, 3 gap. */
+int hgs_field_splat(void* stream, int N, const double* points, const double* dirs, double ox, double oy, double oz, double h, int nx,
+                    int ny, int nz, double r2, long long* acc, int* skipped);
+int hgs_field_solve(void* stream, int nx, int ny, int nz, const long long* acc, double* dir, double* conf);
+int hgs_strand_trace(void* stream, int S, const double* roots, const double* p0, const double* dir, const double* conf, double ox,
+                     double oy, double oz, double h, int nx, int ny, int nz, double step, int max_steps, double cos_max, double min_conf,
+                     int max_gap, double* joints, int* count, int* reason);
+
 /* Tuning knob of the segment-parallel blend (csrc/hgs_blend.hip): tile lists longer than 1.5 segment lengths are walked
  * by one workgroup per segment (the forward walks a list of exactly two segments with one workgroup); the segment length of a pass with R instances is R / target_segments rounded up to a
  * multiple of 64 and clamped to [min_len, max_len] (multiples of 64, min_len >= 128; default 128, 1024, 2048).  Process-wide, takes
