@@ -108,6 +108,7 @@ SIGNATURES = {
     "hgs_field_solve": (ci, [vp, ci, ci, ci, vp, vp, vp]),
     "hgs_strand_trace": (ci, [vp, ci, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, C.c_double, ci,
                               C.c_double, C.c_double, ci, vp, vp, vp]),
+    "hgs_field_fill": (ci, [vp, ci, ci, ci, vp, vp, ci, vp, vp, ci]),
     "hgs_oriented_match_scratch_bytes": (sz, [ci]),
     "hgs_oriented_match": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, sz]),
     "hgs_strand_votes": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]),
@@ -409,6 +410,29 @@ def trace_check(acc=None, shape=None, skipped=None, dir=None, conf=None):
         want = 1 if per is None else nodes * per
         if t.numel() != want:
             raise HgsError(f"{name} holds {t.numel()} values, a grid of {nx} x {ny} x {nz} nodes takes {want}")
+
+
+def fill_check(shape, kind, a, b, free_index):
+    """What hgs_field_fill trusts beyond its own argument checks: kind, a and b are contiguous device tensors of exactly the grid's
+    nodes (a and b six planes of them, two buffers), and free_index is an int32 device tensor of node indices in range.  Returns F."""
+    import torch
+    nx, ny, nz = (int(n) for n in shape)
+    if min(nx, ny, nz) < 2 or max(nx, ny, nz) > 1024 or nx * ny * nz > (1 << 26):
+        raise HgsError(f"a grid of {nx} x {ny} x {nz} nodes (2 to 1024 an axis, at most 2^26 in all)")
+    nodes = nx * ny * nz
+    for t, name, dtype, per in ((kind, "kind", torch.uint8, 1), (a, "a", torch.float64, 6), (b, "b", torch.float64, 6)):
+        require_device_buffer(t, name, dtype)
+        if t.numel() != nodes * per:
+            raise HgsError(f"{name} holds {t.numel()} values, a grid of {nx} x {ny} x {nz} nodes takes {nodes * per}")
+    if a.data_ptr() == b.data_ptr():
+        raise HgsError("a and b are one buffer: the sweep reads one and writes the other")
+    require_device_buffer(free_index, "free_index", torch.int32)
+    F = free_index.numel()
+    if free_index.dim() != 1 or F > nodes:
+        raise HgsError(f"free_index of shape {tuple(free_index.shape)}: [F] with F at most the {nodes} nodes expected")
+    if F and (int(free_index.min()) < 0 or int(free_index.max()) >= nodes):
+        raise HgsError(f"a free index is out of range of the {nodes} nodes")
+    return F
 
 
 KERNEL_COUNT = 18

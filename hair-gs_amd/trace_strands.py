@@ -5,6 +5,7 @@ Stages I and II) and export_strands.py writes as a .hair / .data asset.
   python trace_strands.py -s <scene> -m <model dir>
       [--grid 128] [--radius 1.5] [--step 0.5] [--max_steps 400] [--max_angle 60] [--min_conf 0.5] [--max_gap 4]
       [--roots N] [--points 32] [--min_joints 4] [--min_length 0] [--head_margin 0] [--width 1e-4]
+      [--fill N] [--fill_fixed_conf C] [--fill_domain hull|box] [--fill_min_views 3] [--fill_min_percent 50] [--no_fill_scalp]
       [--field out.npz] [--device cuda|cpu] [--overwrite]
 Reads <scene>/sparse/0/points3D.ply, whose normals init_cloud.py --directions fills with a hair line per point (points with a zero
 normal carry none and are left out), <scene>/head_reconstruction_data.npz (init_scalp.py: the scalp points are the roots, all of them
@@ -18,8 +19,16 @@ defaults are knobs, not measured optima.
 Strands of fewer than --min_joints joints or shorter than --min_length (scene units) are dropped; the others are resampled to --points
 joints at uniform arc length and saved, grey, as <model dir>/point_cloud/iteration_1/point_cloud.ply, next to input.ply and
 cameras.json as a first training run writes them.  A model directory that already holds a point_cloud/ is refused without --overwrite.
---field also saves the direction volume (origin, spacing, shape, dir, conf).  Prints the skipped points, the non-empty nodes, the
-strands per stop reason and the kept / dropped counts; main() returns the number of strands saved."""
+--fill N (default 0: nothing below runs) fills the volume between the scalp and the visible hair before the trace (utils/field_fill.py
+states the arithmetic): the nodes with at least --fill_fixed_conf aligned mass (default: --min_conf) are held fixed, and so are the
+nodes around the scalp points, splatted with their outward directions (--no_fill_scalp leaves those out); N Jacobi sweeps relax the
+tensors d d^T of the nodes between them, and the filled nodes get the direction and the confidence (0 to 1) of the relaxed tensor.
+<scene>/head_sdf.npz is required: the fill stays --head_margin outside the head.  --fill_domain hull also keeps it inside the masks'
+hull (<scene>/masks/, a node votes as a point of init_cloud.py does, --fill_min_views and --fill_min_percent); box fills every node
+outside the head, which suits synthetic scenes.  Prints the fixed, free and out nodes, the largest change of the last sweep and the
+filled nodes that reach --min_conf.
+--field also saves the direction volume (origin, spacing, shape, dir, conf), filled if it was.  Prints the skipped points, the
+non-empty nodes, the strands per stop reason and the kept / dropped counts; main() returns the number of strands saved."""
 import json
 import math
 import os
@@ -52,6 +61,53 @@ def _write_inputs(source_path, model_path, ply_path):
         json.dump([camera_to_json(i, c) for i, c in enumerate(info.cameras)], fh)
 
 
+def fill_allowed(src, field, sdf, head_margin, domain, min_views, min_percent, device):
+    """bool [nz, ny, nx]: the nodes the fill may relax.  Head distance >= head_margin; for the hull also the carve vote of the node
+    positions against the capture's masks, views and masks read as init_cloud.py reads them."""
+    from data import capture
+    from utils import carve
+    from utils import head_sdf as H
+    nodes = field.nodes()
+    d = H.sample(nodes.astype(np.float32), sdf, 0.0)[2].reshape(field.conf.shape)
+    allowed = d >= np.float32(head_margin)
+    if domain == "hull":
+        from utils.views import load_views, read_plane
+        if not os.path.isdir(os.path.join(src, capture.MASKS)):
+            _fail(f"{src} has no {capture.MASKS}/ folder to take the hair's hull from: --fill_domain box fills every node outside the head")
+        try:
+            views = load_views(os.path.join(src, "sparse", "0"))
+            masks = [read_plane(capture.mask_path(src, capture.file_name(v)), v, "the mask") for v in views]
+        except ValueError as e:
+            _fail(str(e))
+        seen, hits = carve.mask_votes(nodes, views, masks, device=device)
+        allowed &= carve.keep(seen, hits, min_views, min_percent).reshape(allowed.shape)
+    return allowed
+
+
+def fill_volume(args, src, field, scalp, head_verts, sdf, device):
+    """Steps 3 to 6 of --fill: the scalp's nodes, the head exclusion, the domain, and the relaxation.  Returns the filled Field."""
+    from utils import field_fill as FF
+    from utils import trace as T
+    fixed_conf = args.min_conf if args.fill_fixed_conf is None else args.fill_fixed_conf
+    if not args.no_fill_scalp:
+        sf = T.build_field(scalp, T.initial_directions(scalp, head_verts), field.origin, field.spacing, field.shape,
+                           args.radius * field.spacing, device=device)
+        take = (sf.conf >= fixed_conf) & (field.conf < fixed_conf)
+        field.dir[take], field.conf[take] = sf.dir[take], sf.conf[take]
+        print(f"{scalp.shape[0]} scalp point(s) splatted with their outward directions: {int(take.sum())} node(s) taken from them")
+    print(f"{T.exclude_head(field, sdf, args.head_margin)} node(s) cleared: closer to the head than {args.head_margin:g}")
+    allowed = fill_allowed(src, field, sdf, args.head_margin, args.fill_domain, args.fill_min_views, args.fill_min_percent, device)
+    kind = FF.classify(field, fixed_conf, allowed)
+    n_fixed, n_free, n_out = FF.counts(kind)
+    print(f"fill ({args.fill_domain}): {n_fixed} fixed, {n_free} free, {n_out} out node(s)")
+    stats = {}
+    filled = FF.fill_field(field, kind, args.fill, device=device, stats=stats)
+    reached = int(((kind == FF.FREE) & (filled.conf >= args.min_conf)).sum())
+    print(f"{args.fill} sweep(s): the last one changed an entry by {stats['last_change']:.3e} at the most; {reached} of {n_free} free node(s) "
+          f"ended with at least {args.min_conf:g}")
+    return filled
+
+
 def main(argv=None, field=None):
     """field: a utils.trace.Field to trace through instead of the one built from the cloud (programs and tests; not an option)."""
     knob = " (a knob, not a measured optimum)"
@@ -72,6 +128,12 @@ def main(argv=None, field=None):
     parser.add_argument("--min_length", type=float, default=0.0, help="drop strands shorter than this, in scene units")
     parser.add_argument("--head_margin", type=float, default=0.0, help="with head_sdf.npz: nodes closer to the head than this take no part")
     parser.add_argument("--width", type=float, default=1e-4, help="initial strand width")
+    parser.add_argument("--fill", type=int, default=0, metavar="N", help="fill the volume between the scalp and the visible hair with N Jacobi sweeps (0: no fill)")
+    parser.add_argument("--fill_fixed_conf", type=float, default=None, metavar="C", help="nodes with at least this aligned mass are held fixed (default: --min_conf)")
+    parser.add_argument("--fill_domain", choices=("hull", "box"), default="hull", help="hull: inside the masks' hull and outside the head; box: every node outside the head")
+    parser.add_argument("--fill_min_views", type=int, default=3, help="the hull's vote rule, as init_cloud.py --min_views")
+    parser.add_argument("--fill_min_percent", type=int, default=50, help="the hull's vote rule, as init_cloud.py --min_percent")
+    parser.add_argument("--no_fill_scalp", action="store_true", help="do not hold the scalp's outward directions fixed")
     parser.add_argument("--field", default=None, metavar="NPZ", help="also save the direction volume")
     parser.add_argument("--device", default="cuda", help="cuda: the HIP kernels; cpu: the numpy path")
     parser.add_argument("--overwrite", action="store_true")
@@ -90,6 +152,9 @@ def main(argv=None, field=None):
                           and (args.roots is None or args.roots >= 1)):
         _fail("--radius > 0, --step > 0, 0 <= --max_angle <= 180, 1 <= --max_steps <= 4096, --max_gap >= 0, --points >= 2, --min_joints >= 2, "
               "--min_length >= 0, --width > 0 and --roots >= 1 expected, all finite")
+    if not 0 <= args.fill <= 65536 or (args.fill_fixed_conf is not None and not math.isfinite(args.fill_fixed_conf)) or args.fill_min_views < 1 \
+            or not 0 <= args.fill_min_percent <= 100:
+        _fail("0 <= --fill <= 65536, a finite --fill_fixed_conf, --fill_min_views >= 1 and 0 <= --fill_min_percent <= 100 expected")
     src, model = args.source_path, args.model_path
     ply_path = os.path.join(src, "sparse", "0", "points3D.ply")
     if not os.path.exists(ply_path):
@@ -118,6 +183,8 @@ def main(argv=None, field=None):
             sdf = H.load_sdf(H.scene_sdf_path(src))
         except ValueError as e:
             _fail(str(e))
+    elif args.fill:
+        _fail(f"{H.scene_sdf_path(src)} is missing: without it --fill would run into the head; run head_sdf.py -s {src} first")
     roots = scalp[carve.select(scalp.shape[0], scalp.shape[0] if args.roots is None else args.roots)]
     p0 = T.initial_directions(roots, head.head_verts)
     points, dirs = points[directed], dirs[directed]
@@ -131,7 +198,9 @@ def main(argv=None, field=None):
         else:
             field = T.Field(field.origin, field.spacing, field.shape, field.dir.copy(), field.conf.copy())
             print(f"a given volume of {field.shape[0]} x {field.shape[1]} x {field.shape[2]} nodes, h {field.spacing:.6g}")
-        if sdf is not None:
+        if args.fill:
+            field = fill_volume(args, src, field, scalp, head.head_verts, sdf, device)
+        elif sdf is not None:
             print(f"{T.exclude_head(field, sdf, args.head_margin)} node(s) cleared: closer to the head than {args.head_margin:g}")
         h = field.spacing
         joints, count, reason = T.trace(roots, p0, field, args.step * h, args.max_steps, math.cos(math.radians(args.max_angle)),

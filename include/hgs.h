@@ -886,6 +886,18 @@ int hgs_strand_trace(void* stream, int S, const double* roots, const double* p0,
                      double oy, double oz, double h, int nx, int ny, int nz, double step, int max_steps, double cos_max, double min_conf,
                      int max_gap, double* joints, int* count, int* reason);
 
+/* The direction volume filled between the scalp and the visible hair (csrc/hgs_fill.hip; utils/field_fill.py states the contract and
+ *   has the numpy path).  All float64, one rounding per operation.  Every argument is checked before a pointer is touched.
+ * hgs_field_fill: `sweeps` Jacobi sweeps (0 to 65536) over the F nodes free_index [F] int32 names (ascending node indices of the
+ *   nodes whose kind is 1), on the grid of hgs_field_splat.  kind [nz][ny][nx] uint8: 0 out, 1 free, 2 fixed.  a and b, [6][nz][ny][nx]
+ *   float64 each (planes xx, xy, xz, yy, yz, zz), both hold the seed on entry; sweep k reads a and writes b for even k, the other way
+ *   round for odd k.  A listed node becomes, per plane, the sum of its face neighbours (-x, +x, -y, +y, -z, +z; one that is off the
+ *   grid or out adds +0.0) divided by the number that counted, or keeps its value where none did; no other node is written.  The
+ *   result is in a for even `sweeps` and in b for odd, the iterate before it in the other buffer.  One plain launch per sweep on
+ *   `stream`, no host synchronisation.  F == 0 or sweeps == 0 launches nothing. */
+int hgs_field_fill(void* stream, int nx, int ny, int nz, const unsigned char* kind, const int* free_index, int F, double* a, double* b,
+                   int sweeps);
+
 /* Tuning knob of the segment-parallel blend (csrc/hgs_blend.hip): tile lists longer than 1.5 segment lengths are walked
  * by one workgroup per segment (the forward walks a list of exactly two segments with one workgroup); the segment length of a pass with R instances is R / target_segments rounded up to a
  * multiple of 64 and clamped to [min_len, max_len] (multiples of 64, min_len >= 128; default 128, 1024, 2048).  Process-wide, takes
