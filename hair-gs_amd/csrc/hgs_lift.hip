@@ -1,5 +1,5 @@
 // hgs_lift.hip -- 3-D hair directions lifted from a capture's 2-D orientation maps (utils/lift.py states the contract, init_cloud.py
-// --directions is the scene driver): hgs_lift_moments, hgs_lift_solve.  gfx950, wave64.
+// --directions is the scene driver): hgs_lift_moments, hgs_lift_moments_gated, hgs_lift_solve.  gfx950, wave64.
 //
 // The contract (one definition for the numpy path, these kernels and the tests' loop restatement).  A view k is a pinhole camera
 // with three uint8 planes [H][W] at the record's mask_offset of three buffers: mask, orient and conf.  TAB[256][2] =
@@ -7,6 +7,7 @@
 // float64, one rounding per operation in the order written (this file is built with -ffp-contract=off):
 //   xc, yc, zc, u, v, seen, px, py as in hgs_pinhole.h
 //   used iff seen and mask[py][px] != 0 and conf[py][px] >= min_conf
+//     (hgs_lift_moments_gated: and bit k % 32 of visible[i][k / 32] is set -- utils/visibility.py's words)
 //   lu = TAB[orient[py][px]][0], lv = TAB[..][1];  a = lu/fx, b = lv/fy
 //   ncx = -(zc*b), ncy = zc*a, ncz = xc*b - yc*a;  n_i = (R0i*ncx + R1i*ncy) + R2i*ncz;  nn = (n0*n0 + n1*n1) + n2*n2
 //   not used unless nn > 0 and nn is finite
@@ -29,11 +30,16 @@
 
 namespace {
 
+// GATED: a view is used only where its bit of the point's visibility words is set (hgs_hull_visibility's layout); the word of the
+// current 32 views is kept in a register, and a view whose bit is clear is left before its projection.  One body for both entry
+// points: the sums of the two instances have the same order.
+template <bool GATED>
 __global__ __launch_bounds__(256) void lift_moments_kernel(long long N, const double* __restrict__ points, int V,
                                                            const HgsCarveView* __restrict__ views, const unsigned char* __restrict__ masks,
                                                            const unsigned char* __restrict__ orients, const unsigned char* __restrict__ confs,
                                                            const double* __restrict__ tab, const double* __restrict__ prev, double s2,
-                                                           int min_conf, double* __restrict__ M, double* __restrict__ wsum_out,
+                                                           int min_conf, const int* __restrict__ visible, int words,
+                                                           double* __restrict__ M, double* __restrict__ wsum_out,
                                                            int* __restrict__ count_out) {
   __shared__ double stab[512];
   stab[threadIdx.x] = tab[threadIdx.x];
@@ -47,7 +53,12 @@ __global__ __launch_bounds__(256) void lift_moments_kernel(long long N, const do
   const bool robust = prev && !(p0 == 0.0 && p1 == 0.0 && p2 == 0.0);
   double m00 = 0.0, m01 = 0.0, m02 = 0.0, m11 = 0.0, m12 = 0.0, m22 = 0.0, wsum = 0.0;
   int count = 0;
+  unsigned gate = 0u;
   for (int k = 0; k < V; k++) {
+    if (GATED) {
+      if ((k & 31) == 0) gate = (unsigned)visible[(size_t)i * words + (k >> 5)];
+      if (!((gate >> (k & 31)) & 1u)) continue;
+    }
     const HgsCarveView& c = views[k];
     const Pinhole q = pinhole_project(c, x, y, z);
     if (!pinhole_seen(&c, q)) continue;
@@ -116,24 +127,46 @@ __global__ __launch_bounds__(256) void lift_solve_kernel(long long N, const doub
 
 }  // namespace
 
+// the checks and the launch of both entry points: `who` names the one that was called, `gated` says that it takes the words
+static int lift_moments_launch(const char* who, void* stream, long long N, const double* points, int V, const HgsCarveView* views_dev,
+                               const unsigned char* masks, const unsigned char* orients, const unsigned char* confs, const double* tab_dev,
+                               const double* prev, double s2, int min_conf, bool gated, const int* visible, int words, double* M,
+                               double* wsum, int* count) {
+  if (N < 0 || N > 0x7FFFFFFFll * 256) { hgs_set_error("%s: N = %lld points", who, N); return 1; }
+  if (V < 1 || V > HGS_LIFT_MAX_VIEWS) { hgs_set_error("%s: V = %d views (1 to %d)", who, V, HGS_LIFT_MAX_VIEWS); return 1; }
+  if (min_conf < 0 || min_conf > 255) { hgs_set_error("%s: min_conf = %d (0 to 255)", who, min_conf); return 1; }
+  if (prev && !(s2 > 0.0 && s2 < __builtin_inf())) {
+    hgs_set_error("%s: s2 = %g with a previous direction (finite and positive)", who, s2); return 1;
+  }
+  if (gated && words != (V + 31) / 32) { hgs_set_error("%s: words = %d, %d views take %d", who, words, V, (V + 31) / 32); return 1; }
+  if (N == 0) return 0;
+  if (!points || !views_dev || !masks || !orients || !confs || !tab_dev || !M || !wsum || !count || (gated && !visible)) {
+    hgs_set_error("%s: null argument", who); return 1;
+  }
+  const dim3 grid((unsigned)((N + 255) / 256)), block(256);
+  if (gated)
+    hipLaunchKernelGGL(lift_moments_kernel<true>, grid, block, 0, (hipStream_t)stream, N, points, V, views_dev, masks, orients, confs,
+                       tab_dev, prev, s2, min_conf, visible, words, M, wsum, count);
+  else
+    hipLaunchKernelGGL(lift_moments_kernel<false>, grid, block, 0, (hipStream_t)stream, N, points, V, views_dev, masks, orients, confs,
+                       tab_dev, prev, s2, min_conf, (const int*)nullptr, 0, M, wsum, count);
+  HGS_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int hgs_lift_moments(void* stream, long long N, const double* points, int V, const HgsCarveView* views_dev,
                                 const unsigned char* masks, const unsigned char* orients, const unsigned char* confs, const double* tab_dev,
                                 const double* prev, double s2, int min_conf, double* M, double* wsum, int* count) {
-  if (N < 0 || N > 0x7FFFFFFFll * 256) { hgs_set_error("hgs_lift_moments: N = %lld points", N); return 1; }
-  if (V < 1 || V > HGS_LIFT_MAX_VIEWS) { hgs_set_error("hgs_lift_moments: V = %d views (1 to %d)", V, HGS_LIFT_MAX_VIEWS); return 1; }
-  if (min_conf < 0 || min_conf > 255) { hgs_set_error("hgs_lift_moments: min_conf = %d (0 to 255)", min_conf); return 1; }
-  if (prev && !(s2 > 0.0 && s2 < __builtin_inf())) {
-    hgs_set_error("hgs_lift_moments: s2 = %g with a previous direction (finite and positive)", s2); return 1;
-  }
-  if (N == 0) return 0;
-  if (!points || !views_dev || !masks || !orients || !confs || !tab_dev || !M || !wsum || !count) {
-    hgs_set_error("hgs_lift_moments: null argument"); return 1;
-  }
-  const dim3 grid((unsigned)((N + 255) / 256)), block(256);
-  hipLaunchKernelGGL(lift_moments_kernel, grid, block, 0, (hipStream_t)stream, N, points, V, views_dev, masks, orients, confs, tab_dev,
-                     prev, s2, min_conf, M, wsum, count);
-  HGS_CHECK_LAUNCH();
-  return 0;
+  return lift_moments_launch("hgs_lift_moments", stream, N, points, V, views_dev, masks, orients, confs, tab_dev, prev, s2, min_conf, false,
+                             nullptr, 0, M, wsum, count);
+}
+
+extern "C" int hgs_lift_moments_gated(void* stream, long long N, const double* points, int V, const HgsCarveView* views_dev,
+                                      const unsigned char* masks, const unsigned char* orients, const unsigned char* confs,
+                                      const double* tab_dev, const double* prev, double s2, int min_conf, const int* visible, int words,
+                                      double* M, double* wsum, int* count) {
+  return lift_moments_launch("hgs_lift_moments_gated", stream, N, points, V, views_dev, masks, orients, confs, tab_dev, prev, s2, min_conf,
+                             true, visible, words, M, wsum, count);
 }
 
 extern "C" int hgs_lift_solve(void* stream, long long N, const double* M, const int* count, int min_views, double* d,

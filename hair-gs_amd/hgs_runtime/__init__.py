@@ -98,6 +98,8 @@ SIGNATURES = {
     "hgs_carve_shell": (ci, [vp, ci, ci, ci, vp, vp]),
     "hgs_lift_moments": (ci, [vp, C.c_longlong, vp, ci, vp, vp, vp, vp, vp, vp, C.c_double, ci, vp, vp, vp]),
     "hgs_lift_solve": (ci, [vp, C.c_longlong, vp, vp, ci, vp, vp]),
+    "hgs_lift_moments_gated": (ci, [vp, C.c_longlong, vp, ci, vp, vp, vp, vp, vp, vp, C.c_double, ci, vp, ci, vp, vp, vp]),
+    "hgs_hull_visibility": (ci, [vp, C.c_longlong, vp, ci, vp, vp, vp, C.c_double, ci, ci, ci, ci, ci, vp]),
     "hgs_scalp_depth": (ci, [vp, ci, vp, ci, vp, ci, vp, vp, vp]),
     "hgs_scalp_votes": (ci, [vp, C.c_longlong, vp, vp, ci, vp, vp, vp, C.c_double, C.c_double, vp, vp]),
     "hgs_mesh_sdf": (ci, [vp, ci, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, vp, vp]),
@@ -361,10 +363,11 @@ def carve_check(records, views_dev, masks, images=None):
     return len(_carve_planes(records, views_dev, masks, images))
 
 
-def lift_check(records, views_dev, masks, orients, confs, tab, images=None):
+def lift_check(records, views_dev, masks, orients, confs, tab, images=None, visible=None, N=None):
     """What hgs_lift_moments may not be called without (include/hgs.h): carve_check's guarantee for the masks, extended to the
     orientation and confidence buffers (addressed by the same mask_offset), and a float64 table of 256 x 2 entries.  `images`: the
-    image buffer of records that name one (the lift does not read it).  Returns the number of views."""
+    image buffer of records that name one (the lift does not read it).  `visible` (hgs_lift_moments_gated): the word buffer, an
+    int32 device tensor of exactly [N, ceil(V/32)].  Returns the number of views."""
     import torch
     planes = _carve_planes(records, views_dev, masks, images)
     for name, buf in (("orients", orients), ("confs", confs)):
@@ -373,7 +376,38 @@ def lift_check(records, views_dev, masks, orients, confs, tab, images=None):
     require_device_buffer(tab, "tab", torch.float64)
     if tab.numel() != 512:
         raise HgsError(f"the sine / cosine table holds {tab.numel()} values, 256 x 2 expected")
+    if visible is not None:
+        _words_check(visible, N, len(planes))
     return len(planes)
+
+
+def _words_check(visible, N, V):
+    """The visibility words of N points and V views: a contiguous int32 device tensor [N, ceil(V/32)]."""
+    import torch
+    require_device_buffer(visible, "visible", torch.int32)
+    if tuple(visible.shape) != (int(N), (V + 31) // 32):
+        raise HgsError(f"visible of shape {tuple(visible.shape)}: [{int(N)}, {(V + 31) // 32}] expected for {V} views")
+
+
+def visibility_check(shape, occ, points, centres, visible):
+    """What hgs_hull_visibility trusts beyond its own argument checks, in front of every launch: occ is a contiguous uint8 device tensor
+    of exactly the grid's voxels, points and centres float64 [N, 3] and [V, 3], visible int32 [N, ceil(V/32)].  Returns (N, V)."""
+    import torch
+    nx, ny, nz = (int(n) for n in shape)
+    if min(nx, ny, nz) < 1 or max(nx, ny, nz) > 1024:
+        raise HgsError(f"a grid of {nx} x {ny} x {nz} voxels (1 to 1024 per axis)")
+    require_device_buffer(occ, "occ", torch.uint8)
+    if occ.numel() != nx * ny * nz:
+        raise HgsError(f"occ holds {occ.numel()} bytes, a grid of {nx} x {ny} x {nz} voxels takes {nx * ny * nz}")
+    for t, name in ((points, "points"), (centres, "centres")):
+        require_device_buffer(t, name, torch.float64)
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise HgsError(f"{name} of shape {tuple(t.shape)}: [{'N' if name == 'points' else 'V'}, 3] expected")
+    N, V = points.shape[0], centres.shape[0]
+    if not 1 <= V <= 4096:
+        raise HgsError(f"{V} views (1 to 4096)")
+    _words_check(visible, N, V)
+    return N, V
 
 
 def scalp_check(records, views_dev, masks, depth, faces=None, n_verts=None):

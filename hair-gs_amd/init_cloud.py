@@ -4,7 +4,8 @@ cloud is sparse where hair is and dense on the face, the shoulders and the backg
   python init_cloud.py -s <scene> [--mode hull|filter|both] [--grid 256] [--bounds x0 y0 z0 x1 y1 z1]
                        [--min_views 3] [--min_percent 50] [--dilate 0] [--no_shell] [--max_points 200000]
                        [--images images] [--device cuda|cpu] [--overwrite]
-                       [--directions [--orientations orientations] [--rounds 3] [--sigma_deg 10] [--min_conf 1] [--min_coherence 0]]
+                       [--directions [--orientations orientations] [--rounds 3] [--sigma_deg 10] [--min_conf 1] [--min_coherence 0]
+                                     [--visibility [--vis_skip 1] [--vis_max_blocked 0]]]
 Reads <scene>/sparse/0 (binary or text; PINHOLE and SIMPLE_PINHOLE cameras only -- undistort.py makes them), <scene>/masks/<name> for
 every image of the model and, for the hull's colours, <scene>/<images>/<name> (data/capture.py forms the names, as for the loader).
   hull    a --grid voxel grid over the automatic bounds (utils.carve.auto_bounds) or over --bounds is tested against every mask; a voxel
@@ -26,7 +27,12 @@ arithmetic): <scene>/<orientations>/<stem>_orientation.png and _confidence.png o
 views that have the point in frame, on the (dilated) mask and with a confidence of at least --min_conf vote in --rounds re-weighted
 rounds of scale --sigma_deg, and sparse/0/points3D.ply is written with the same points and colours and the direction in nx, ny, nz --
 zero where fewer than two views determine it or its coherence is below --min_coherence.  The loader reads that file as it is, and
-training with --init_directions starts from Gaussians stretched along it.  Without the flag no points3D.ply is written."""
+training with --init_directions starts from Gaussians stretched along it.  Without the flag no points3D.ply is written.
+--visibility (with --directions, modes hull and both) lets a view vote for a point's direction only where it can see the point: a ray
+from the point to the camera is marched through the solid carved grid (utils/visibility.py states the arithmetic), and a view whose
+ray meets more than --vis_max_blocked occupied voxels further than --vis_skip voxels from the point's own is left out.  A filtered
+COLMAP point outside the grid is unoccluded.  A point left with fewer than two views gets the zero direction; the counts are printed.
+Without the flag every file is written as before."""
 import os
 import sys
 
@@ -50,16 +56,37 @@ def _fail(msg):
     raise SystemExit(f"init_cloud.py: {msg}")
 
 
-def lift_normals(voter, orients, confs, xyz, args):
-    """(normals f64 [n, 3], coherence f64 [n]) of the written points: utils.lift's directions, zero below --min_coherence."""
-    from utils import lift
+def lift_normals(voter, orients, confs, xyz, args, grid=None):
+    """(normals f64 [n, 3], coherence f64 [n]) of the written points: utils.lift's directions, zero below --min_coherence.  grid
+    (origin, h, dims, occ), the solid carved grid: the votes are gated by utils.visibility's march through it, and what the gate did is
+    printed."""
+    from utils import lift, visibility
+    knobs = (args.rounds, args.sigma_deg, args.min_conf)
+    visible = plain = None
     if voter.device is None:
-        d, coherence, _ = lift.lift_directions(xyz, voter.views, voter.masks, orients, confs, args.rounds, args.sigma_deg, args.min_conf)
+        if grid is not None:
+            origin, h, _, occ = grid
+            visible = visibility.visibility_numpy(xyz, visibility.camera_centres(voter.views), occ, origin, h, args.vis_skip, args.vis_max_blocked)
+            plain = lift.moments_numpy(xyz, voter.views, voter.masks, orients, confs, min_conf=args.min_conf)[2]
+        d, coherence, count = lift.lift_directions(xyz, voter.views, voter.masks, orients, confs, *knobs, visible=visible)
     else:
+        import torch
         from utils.views import upload_points
         packed = lift.pack(voter.views, voter.masks, orients, confs, voter.device, carve_packed=voter.packed)
         pts = upload_points(xyz, voter.device)
-        d, coherence, _ = (t.cpu().numpy() for t in lift.directions_device(pts, packed, args.rounds, args.sigma_deg, args.min_conf))
+        words = None
+        if grid is not None:
+            origin, h, _, occ = grid
+            centres = visibility.upload_centres(visibility.camera_centres(voter.views), voter.device)
+            words = visibility.visibility_device(pts, centres, torch.from_numpy(occ).to(voter.device), origin, h, args.vis_skip,
+                                                 args.vis_max_blocked)
+            visible = words.cpu().numpy()
+            plain = lift.moments_device(pts, packed, min_conf=args.min_conf)[2].cpu().numpy()
+        d, coherence, count = (t.cpu().numpy() for t in lift.directions_device(pts, packed, *knobs, visible=words))
+    if grid is not None:                                         # (plain: the views the lift would use without the gate)
+        on_mask, seen = visibility.pair_counts(xyz, voter.views, voter.masks, visible)
+        print(f"visibility (skip {args.vis_skip}, max_blocked {args.vis_max_blocked}): {on_mask} (point, view) pair(s) in frame and on the mask, "
+              f"{seen} of them visible; {int(((plain >= 2) & (count < 2)).sum())} point(s) lost their direction to the gate")
     return np.where((coherence >= args.min_coherence)[:, None], d, 0.0), coherence
 
 
@@ -118,7 +145,7 @@ def hull_grid(voter, bounds, grid, min_views, min_percent):
 
 
 def hull_points(voter, args):
-    """(xyz f64 [n, 3], rgb u8 [n, 3]) of the carved grid; prints what it did."""
+    """(xyz f64 [n, 3], rgb u8 [n, 3], (origin, h, dims, occ)) of the carved grid, occ the solid one; prints what it did."""
     lo, hi, how, origin, h, dims, occ = hull_grid(voter, args.bounds, args.grid, args.min_views, args.min_percent)
     kept = int(np.count_nonzero(occ))
     out = occ if args.no_shell else voter.shell(occ)
@@ -132,7 +159,7 @@ def hull_points(voter, args):
     print(f"bounds ({how}): {lo.tolist()} .. {hi.tolist()}")
     print(f"grid {nx} x {ny} x {nz}, voxel size {h:.6g}: {kept} kept, {n_shell} {'kept (no shell)' if args.no_shell else 'on the shell'}, "
           f"{flat.size} written")
-    return xyz, mean_colours(rgb_sum, hits)
+    return xyz, mean_colours(rgb_sum, hits), (origin, h, dims, occ)
 
 
 def main(argv=None):
@@ -156,6 +183,9 @@ def main(argv=None):
     parser.add_argument("--sigma_deg", type=float, default=10.0, help="angular scale of the re-weighting")
     parser.add_argument("--min_conf", type=int, default=1, help="smallest confidence byte (0 to 255) that votes")
     parser.add_argument("--min_coherence", type=float, default=0.0, help="directions below this coherence are written as zero")
+    parser.add_argument("--visibility", action="store_true", help="with --directions: only views that see a point through the carved hull vote")
+    parser.add_argument("--vis_skip", type=int, default=1, help="occupied voxels within this many voxels of the point's own do not block")
+    parser.add_argument("--vis_max_blocked", type=int, default=0, help="occupied voxels a ray may meet before its view is left out")
     args = parser.parse_args(argv)
     from data.colmap import read_points3D_binary, read_points3D_text, write_points3D_arrays
     from utils import carve
@@ -166,6 +196,14 @@ def main(argv=None):
         _fail(f"--min_views >= 1, 0 <= --min_percent <= 100, --dilate >= 0, --max_points >= 1 and 1 <= --grid <= {carve.MAX_DIM} expected")
     if args.directions and (args.rounds < 0 or not 0 <= args.min_conf <= 255 or not 0.0 < args.sigma_deg < 180.0):
         _fail("--rounds >= 0, 0 <= --min_conf <= 255 and 0 < --sigma_deg < 180 expected")
+    if args.visibility:
+        from utils import visibility
+        if not args.directions:
+            _fail("--visibility gates the votes of --directions: pass both")
+        if args.mode == "filter":
+            _fail("--visibility marches the carved grid, and --mode filter carves none: use --mode hull or both")
+        if not 0 <= args.vis_skip <= visibility.MAX_SKIP or not 0 <= args.vis_max_blocked <= visibility.MAX_BLOCKED:
+            _fail(f"0 <= --vis_skip <= {visibility.MAX_SKIP} and 0 <= --vis_max_blocked <= {visibility.MAX_BLOCKED} expected")
     src = args.source_path
     sparse = os.path.join(src, "sparse", "0")
     if not os.path.isdir(os.path.join(src, capture.MASKS)):
@@ -191,7 +229,7 @@ def main(argv=None):
     except ValueError as e:
         _fail(str(e))
     voter = _Voter(views, masks, imgs, None if args.device == "cpu" else "cuda", args.dilate)
-    parts = []
+    parts, grid = [], None
     if args.mode in ("filter", "both"):
         source = backup or original
         if source is None:
@@ -202,7 +240,7 @@ def main(argv=None):
         print(f"filter: {int(k.sum())} of {xyz.shape[0]} COLMAP point(s) kept")
         parts.append((xyz[k], rgb[k].astype(np.uint8), err.reshape(-1)[k]))
     if args.mode in ("hull", "both"):
-        xyz, rgb = hull_points(voter, args)
+        xyz, rgb, grid = hull_points(voter, args)
         parts.append((xyz, rgb, np.zeros(xyz.shape[0], np.float64)))
     xyz, rgb, err = (np.concatenate([p[i] for p in parts]) for i in range(3))
     tmp = f"{result}.{os.getpid()}.tmp"
@@ -219,7 +257,7 @@ def main(argv=None):
     print(f"{n} point(s) written to {result}")
     if args.directions:
         from data.dataset_readers import storePly
-        normals, coherence = lift_normals(voter, orients, confs, xyz, args)
+        normals, coherence = lift_normals(voter, orients, confs, xyz, args, grid if args.visibility else None)
         has = (normals != 0.0).any(axis=1)
         tmp = f"{ply}.{os.getpid()}.tmp"                         # (under a private name and renamed, as the loader writes it)
         storePly(tmp, xyz, rgb, normals)

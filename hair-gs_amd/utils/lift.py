@@ -13,6 +13,9 @@ on the host in float64 (table()) and handed to both backends: no transcendental 
 
 Sample of a point (x, y, z) in view k.  xc, yc, zc, u, v, seen, px, py by utils/views.py's projection contract:
     used  iff  seen  and  mask[py, px] != 0  and  conf[py, px] >= min_conf       (min_conf: an integer, 0 to 255, default 1)
+With visible (utils/visibility.py's words, int32 [N, ceil(V/32)]; None: no gate) a view is used only where, in addition, bit k % 32
+of visible[i, k // 32] is set.  A point left with fewer than min_views used views gets the zero direction like any other such point:
+there is no fallback to the ungated fit.  With every bit set the results are those without the gate, bit for bit.
 
 The plane through the camera centre that contains the point's ray and the image line, with o = orient[py, px]:
     lu = TAB[o][0], lv = TAB[o][1];   a = lu/fx,  b = lv/fy
@@ -43,9 +46,10 @@ re-weighted rounds follow round 0 (rounds = 0 is the plain least-squares fit).  
 rounds = 3 and sigma = 10 degrees are knobs, not measured optima: a numpy prototype gave, at 16 ring views with half of the views
 given a random angle, a median error of 14 degrees after round 0, 2.9 after three re-weighted rounds and 2.6 after four.
 
-Known limits.  "Used" means in frame, on the mask and confident, not unoccluded: a far-side view contributes the orientation of
-whatever hair it sees at that pixel, and the re-weighting is the only defence against that.  A direction along the common viewing
-axis of all its views is poorly determined.
+Known limits.  Without the gate "used" means in frame, on the mask and confident, not unoccluded: a far-side view contributes the
+orientation of whatever hair it sees at that pixel, and the re-weighting is the only defence against that.  The gate is the other
+one: utils/visibility.py marches the carved hull from the point to every camera, and init_cloud.py --directions --visibility hands
+its words to the lift.  A direction along the common viewing axis of all its views is poorly determined.
 
 device=None: numpy.  device="cuda": the kernels, on device tensors.  The caller chooses; neither falls back to the other."""
 import math
@@ -53,6 +57,7 @@ import math
 import numpy as np
 
 from utils.views import camera, check_planes, check_views, is_cuda, pack as pack_views, pixel, upload_planes, upload_points
+from utils.visibility import check_words, view_bit
 
 
 def table():
@@ -113,10 +118,12 @@ def _accumulate(acc, view, cam, used, o, c, tab, prev, s2):
     count += used
 
 
-def _moments_loop(points, views, prev, s2, sample):
+def _moments_loop(points, views, prev, s2, sample, visible=None):
     points = np.asarray(points, np.float64).reshape(-1, 3)
     N = points.shape[0]
     prev = _check_prev(prev, N)
+    if visible is not None:
+        visible = check_words(visible, N, len(views))
     if prev is not None and not (math.isfinite(s2) and s2 > 0.0):
         raise ValueError(f"s2 = {s2}: finite and positive expected with a previous direction")
     tab = table()
@@ -126,11 +133,13 @@ def _moments_loop(points, views, prev, s2, sample):
         for k, view in enumerate(views):
             cam = camera(view, x, y, z)
             used, o, c = sample(k, view, cam)
+            if visible is not None:
+                used = used & view_bit(visible, k)
             _accumulate(acc, view, cam, used, o.astype(np.int64), c.astype(np.float64), tab, prev, s2)
     return acc
 
 
-def moments_numpy(points, views, masks, orients, confs, prev=None, s2=0.0, min_conf=1):
+def moments_numpy(points, views, masks, orients, confs, prev=None, s2=0.0, min_conf=1, visible=None):
     _check_planes(views, masks, orients, confs)
     min_conf, _ = _check_knobs(min_conf)
 
@@ -138,17 +147,17 @@ def moments_numpy(points, views, masks, orients, confs, prev=None, s2=0.0, min_c
         seen, py, px = pixel(view, *cam)
         c = confs[k][py, px]
         return seen & (masks[k][py, px] != 0) & (c >= min_conf), orients[k][py, px], c
-    return _moments_loop(points, views, prev, s2, sample)
+    return _moments_loop(points, views, prev, s2, sample, visible)
 
 
-def moments_from_samples(points, views, used, orient, conf, prev=None, s2=0.0):
+def moments_from_samples(points, views, used, orient, conf, prev=None, s2=0.0, visible=None):
     """The moments without planes: used bool [V, N], orient and conf uint8 [V, N] give every (view, point) its sample directly (a point
     out of a view's frame is still not used)."""
     used, orient, conf = np.asarray(used, bool), np.asarray(orient, np.uint8), np.asarray(conf, np.uint8)
 
     def sample(k, view, cam):
         return used[k] & pixel(view, *cam)[0], orient[k], conf[k]
-    return _moments_loop(points, views, prev, s2, sample)
+    return _moments_loop(points, views, prev, s2, sample, visible)
 
 
 def symmetric(M):
@@ -196,8 +205,9 @@ def pack(views, masks, orients, confs, device="cuda", carve_packed=None):
     return Packed(carve_packed, upload_planes(orients, device), upload_planes(confs, device), torch.from_numpy(table()).to(device))
 
 
-def moments_device(points, packed, prev=None, s2=0.0, min_conf=1):
-    """hgs_lift_moments on a float64 device tensor [N, 3]: (M [N, 6] f64, wsum [N] f64, count [N] i32) on its device."""
+def moments_device(points, packed, prev=None, s2=0.0, min_conf=1, visible=None):
+    """hgs_lift_moments on a float64 device tensor [N, 3]: (M [N, 6] f64, wsum [N] f64, count [N] i32) on its device.  With visible
+    (an int32 device tensor [N, ceil(V/32)]): hgs_lift_moments_gated."""
     import torch
     import hgs_runtime as rt
     rt.require_device_buffer(points, "points", torch.float64)
@@ -209,16 +219,19 @@ def moments_device(points, packed, prev=None, s2=0.0, min_conf=1):
         if tuple(prev.shape) != (N, 3):
             raise rt.HgsError(f"prev of shape {tuple(prev.shape)}: [{N}, 3] expected")
     V = rt.lift_check(packed.carve.records, packed.carve.views_dev, packed.carve.masks_dev, packed.orients_dev, packed.confs_dev,
-                      packed.tab_dev, packed.carve.images_dev)
+                      packed.tab_dev, packed.carve.images_dev, visible, N)
     M = torch.empty((N, 6), dtype=torch.float64, device=points.device)
     wsum = torch.empty(N, dtype=torch.float64, device=points.device)
     count = torch.empty(N, dtype=torch.int32, device=points.device)
+    head = (rt.current_stream(), N, rt.ptr(points), V, rt.ptr(packed.carve.views_dev), rt.ptr(packed.carve.masks_dev),
+            rt.ptr(packed.orients_dev), rt.ptr(packed.confs_dev), rt.ptr(packed.tab_dev), rt.ptr(prev),
+            float(s2) if prev is not None else 0.0, int(min_conf))
+    tail = (rt.ptr(M), rt.ptr(wsum), rt.ptr(count))
     with torch.cuda.device(points.device):
-        rt.check(rt.lib().hgs_lift_moments(rt.current_stream(), N, rt.ptr(points), V, rt.ptr(packed.carve.views_dev),
-                                           rt.ptr(packed.carve.masks_dev), rt.ptr(packed.orients_dev), rt.ptr(packed.confs_dev),
-                                           rt.ptr(packed.tab_dev), rt.ptr(prev),
-                                           float(s2) if prev is not None else 0.0, int(min_conf), rt.ptr(M), rt.ptr(wsum),
-                                           rt.ptr(count)))
+        if visible is None:
+            rt.check(rt.lib().hgs_lift_moments(*head, *tail))
+        else:
+            rt.check(rt.lib().hgs_lift_moments_gated(*head, rt.ptr(visible), visible.shape[1], *tail))
     return M, wsum, count
 
 
@@ -238,12 +251,12 @@ def solve_device(M, count, min_views=2):
     return d, coherence
 
 
-def directions_device(points, packed, rounds=3, sigma_deg=10.0, min_conf=1, min_views=2):
+def directions_device(points, packed, rounds=3, sigma_deg=10.0, min_conf=1, min_views=2, visible=None):
     """The rounds on device tensors: (d, coherence, count)."""
     s2 = sin2(sigma_deg)
     prev = None
     for _ in range(_check_rounds(rounds) + 1):
-        M, _, count = moments_device(points, packed, prev, s2, min_conf)
+        M, _, count = moments_device(points, packed, prev, s2, min_conf, visible)
         prev, coherence = solve_device(M, count, min_views)
     return prev, coherence, count
 
@@ -255,13 +268,21 @@ def _check_rounds(rounds):
     return int(rounds)
 
 
-def lift_moments(points, views, masks, orients, confs, prev=None, s2=0.0, min_conf=1, device=None):
-    """(M f64 [N, 6], wsum f64 [N], count i32 [N]); host arrays."""
+def _upload_words(visible, device):
+    """The visibility words (a host int32 array [N, W], or None) as a device tensor."""
+    if visible is None:
+        return None
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(visible)).to(device)
+
+
+def lift_moments(points, views, masks, orients, confs, prev=None, s2=0.0, min_conf=1, device=None, visible=None):
+    """(M f64 [N, 6], wsum f64 [N], count i32 [N]); host arrays.  visible: utils/visibility.py's words, int32 [N, ceil(V/32)]."""
     if not is_cuda(device):
-        return moments_numpy(points, views, masks, orients, confs, prev, s2, min_conf)
+        return moments_numpy(points, views, masks, orients, confs, prev, s2, min_conf, visible)
     pts = upload_points(points, device)
     out = moments_device(pts, pack(views, masks, orients, confs, device), None if prev is None else upload_points(prev, device), s2,
-                         min_conf)
+                         min_conf, _upload_words(visible, device))
     return tuple(t.cpu().numpy() for t in out)
 
 
@@ -275,16 +296,16 @@ def lift_solve(M, count, min_views=2, device=None):
     return tuple(t.cpu().numpy() for t in solve_device(M, count, min_views))
 
 
-def lift_directions(points, views, masks, orients, confs, rounds=3, sigma_deg=10.0, min_conf=1, min_views=2, device=None):
+def lift_directions(points, views, masks, orients, confs, rounds=3, sigma_deg=10.0, min_conf=1, min_views=2, device=None, visible=None):
     """(d f64 [N, 3], coherence f64 [N], count i32 [N]) of the last round; host arrays."""
     rounds = _check_rounds(rounds)
     if is_cuda(device):
         out = directions_device(upload_points(points, device), pack(views, masks, orients, confs, device), rounds, sigma_deg, min_conf,
-                                min_views)
+                                min_views, _upload_words(visible, device))
         return tuple(t.cpu().numpy() for t in out)
     s2 = sin2(sigma_deg)
     prev = None
     for _ in range(rounds + 1):
-        M, _, count = moments_numpy(points, views, masks, orients, confs, prev, s2, min_conf)
+        M, _, count = moments_numpy(points, views, masks, orients, confs, prev, s2, min_conf, visible)
         prev, coherence = solve_numpy(M, count, min_views)
     return prev, coherence, count

@@ -727,6 +727,34 @@ int hgs_lift_moments(void* stream, long long N, const double* points, int V, con
                      const unsigned char* orients, const unsigned char* confs, const double* tab_dev, const double* prev, double s2,
                      int min_conf, double* M, double* wsum, int* count);
 int hgs_lift_solve(void* stream, long long N, const double* M, const int* count, int min_views, double* d, double* coherence);
+/* hgs_lift_moments_gated: hgs_lift_moments with one more condition of `used`: bit k % 32 of visible[i][k / 32] is set (visible: int32
+ *   [N][words], hgs_hull_visibility's words; words must be ceil(V/32), a null visible is an error).  The same kernel body, the same order
+ *   of the sums; with every bit below V set the outputs are hgs_lift_moments' bit for bit.  hgs_runtime.lift_check guarantees that visible
+ *   holds N*words values. */
+int hgs_lift_moments_gated(void* stream, long long N, const double* points, int V, const HgsCarveView* views_dev, const unsigned char* masks,
+                           const unsigned char* orients, const unsigned char* confs, const double* tab_dev, const double* prev, double s2,
+                           int min_conf, const int* visible, int words, double* M, double* wsum, int* count);
+
+/* hgs_hull_visibility (csrc/hgs_visibility.hip) <-> which views can see a point of the carved hull (utils/visibility.py states the contract,
+ *   init_cloud.py --directions --visibility is the driver; the reference has no such step).  occ[nz][ny][nx] is hgs_carve_grid's uint8
+ *   buffer: voxel i spans origin_host + i*h .. origin_host + (i + 1)*h per axis.  centres_dev[V][3]: the camera centres -R^T t, float64,
+ *   computed on the host.  For the point p and the centre C, float64, one rounding per operation in this order:
+ *     t_a = (p_a - origin_a)/h;  inside iff 0 <= t_a < n_a on every axis (a NaN fails; the test precedes the conversion to an integer);
+ *     a point that does not start inside has every bit below V set.  Otherwise i0_a = (int)floor(t_a), D = C - p and per axis
+ *       D_a > 0:  step = +1, tmax = ((origin_a + (i0_a + 1)*h) - p_a)/D_a, td = h/D_a
+ *       D_a < 0:  step = -1, tmax = ((origin_a + i0_a*h) - p_a)/D_a,       td = h/(-D_a)
+ *       D_a == 0: step = 0,  tmax = +inf
+ *     walk from i = i0, blocked = 0:  a = the axis of the smallest tmax (strict <: the lowest axis wins a tie);  VISIBLE unless tmax_a < 1.0;
+ *     i_a += step_a, VISIBLE if i_a has left the grid;  tmax_a = tmax_a + td_a;  if max_a |i_a - i0_a| > skip and occ[i] != 0: blocked += 1,
+ *     BLOCKED if blocked > max_blocked;  at most nx + ny + nz steps (unreachable: the indices move monotonically), then VISIBLE.
+ *   visible int32 [N][ceil(V/32)]: bit k % 32 of word k / 32 is set iff view k is not blocked; the bits at and above V are 0.
+ *   One lane per (point, word); no atomics: bitwise repeatable and equal to the numpy path.  N == 0 launches nothing.
+ *   Errors before any launch, the text beginning with the function's name: a null buffer, V outside 1..4096, an axis outside 1..1024, skip
+ *   outside 0..1024, max_blocked outside 0..3072, h or 1/h not finite and positive, an origin that is not finite.  The kernel trusts the
+ *   shapes: the caller (hgs_runtime.visibility_check) guarantees occ holds nx*ny*nz bytes, points N*3, centres V*3 and visible
+ *   N*ceil(V/32) values. */
+int hgs_hull_visibility(void* stream, long long N, const double* points, int V, const double* centres_dev, const unsigned char* occ,
+                        const double* origin_host, double h, int nx, int ny, int nz, int skip, int max_blocked, int* visible);
 
 /* hgs_scalp_depth / hgs_scalp_votes (csrc/hgs_scalp.hip) <-> the scalp labelled on a capture's head mesh from its hair masks (utils/scalp.py
  *   states the contract, init_scalp.py is the driver; the reference takes FLAME's fixed scalp region).  The views are HgsCarveView records;
