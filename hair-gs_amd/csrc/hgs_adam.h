@@ -3,7 +3,8 @@
 //   * adam_kernel (hgs_optim.hip, hgs_adam_step): every parameter tensor in one launch, and
 //   * the backward's own lanes (round 5, include/hgs.h HgsAdamSlot): the lane that has just finished the gradient of a parameter
 //     element applies that element's update at once -- preprocess_bwd_kernel's per-Gaussian lanes (width / opacity / mask / SH DC of
-//     a strand model; xyz / scaling / rotation / opacity / mask / SH DC of a cloud) and the endpoint lanes of strand_gather_kernel --
+//     a strand model; xyz / scaling / rotation / opacity / mask / SH DC of a cloud) and the endpoint lanes of strand_gather_kernel (with
+//     a block plan: of preprocess_bwd_kernel's own endpoint phase) --
 //     so that a single-rank iteration has no optimizer launch at all.
 // Evaluated operation by operation (no contraction) in every translation unit: the two forms give the same bits, a run may mix
 // them (captured replays with the in-lane update, eager topology iterations with the launch).

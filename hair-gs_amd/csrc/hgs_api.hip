@@ -310,7 +310,8 @@ static int backward_impl(void* stream, int P, int D, int M, int R, int W, int H,
                          const void* geom_buf, const void* binning_buf, const void* image_buf,
                          const float* const* dL_dpix_planes, void* scratch, float* dL_dextra, float* dL_dmeans2D, float* dL_dconic,
                          float* dL_dopacity, float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                         float* dL_dscales, float* dL_drotations, const HgsParamBackward* pb) {
+                         float* dL_dscales, float* dL_drotations, const HgsParamBackward* pb,
+                         const HgsBlockPlan* plan = nullptr) {
   hipStream_t s = (hipStream_t)stream;
   if (n_extra != 0 && n_extra != 4) { hgs_set_error("n_extra must be 0 or 4 (got %d)", n_extra); return 1; }
   if ((flags & HGS_ROWS_INLINE) && (flags & HGS_ROWS_REDUCE)) { hgs_set_error("HGS_ROWS_INLINE and HGS_ROWS_REDUCE exclude each other"); return 1; }
@@ -357,7 +358,7 @@ static int backward_impl(void* stream, int P, int D, int M, int R, int W, int H,
   a.dL_drotations = dL_drotations;
   a.n_extra = n_extra; a.dL_dextra = dL_dextra;
   a.row_sums = row_sums; a.row_partials = row_partials;
-  return hgs_launch_preprocess_bwd(s, a, g, b, inst_grad, R, im.status, pb);
+  return hgs_launch_preprocess_bwd(s, a, g, b, inst_grad, R, im.status, pb, plan);
 }
 
 size_t hgs_param_forward_bytes(void) { return sizeof(HgsParamForward); }
@@ -372,12 +373,54 @@ static int check_adam_inline(const HgsAdamInline& a, int n_slots, const char* wh
   }
   return 0;
 }
+size_t hgs_block_plan_bytes(void) { return sizeof(HgsBlockPlan); }
+// what the host can see of a block plan (its tables live in device memory: the kernel clamps what it reads from them)
+static int check_block_plan(const HgsBlockPlan& pl, int P, const HgsParamBackward& pb) {
+  const char* who = "hgs_backward_multi_params_planned";
+  if (pb.kind != HGS_PARAMS_HAIR) { hgs_set_error("%s: a block plan needs params->kind == HGS_PARAMS_HAIR", who); return 1; }
+  if (pl.n_chunks <= 0 || pl.n_segments != P || pl.n_endpoints <= 0) {
+    hgs_set_error("%s: plan of %d chunks over %d segments and %d endpoints for a pass of %d Gaussians", who, pl.n_chunks,
+                  pl.n_segments, pl.n_endpoints, P);
+    return 1;
+  }
+  // (a chunk holds at most 256 segments and 256 endpoints, and at least one segment)
+  if ((long long)pl.n_chunks * HGS_BLOCK < (long long)P || (long long)pl.n_chunks * HGS_BLOCK < (long long)pl.n_endpoints || pl.n_chunks > P) {
+    hgs_set_error("%s: %d chunks cannot hold %d segments and %d endpoints", who, pl.n_chunks, P, pl.n_endpoints);
+    return 1;
+  }
+  if (!pl.chunks || !pl.ep_list || !pl.ep_segments || !pl.d_endpoints) { hgs_set_error("%s: null plan table, ep_segments or d_endpoints", who); return 1; }
+  if (((size_t)pl.chunks & 15) || ((size_t)pl.ep_list & 3) || ((size_t)pl.ep_segments & 7) || ((size_t)pl.ep_pairs & 15) ||
+      ((size_t)pl.smooth_pair_grads & 15) || ((size_t)pl.d_endpoints & 3)) {
+    hgs_set_error("%s: unaligned plan table (chunks, ep_pairs, smooth_pair_grads: 16 bytes; ep_segments: 8)", who);
+    return 1;
+  }
+  if (pl.n_smooth < 0) { hgs_set_error("%s: n_smooth %d", who, pl.n_smooth); return 1; }
+  if (pl.n_smooth > 0 && pl.ep_pairs) {
+    if (!pl.head_out || !pl.grad_out) { hgs_set_error("%s: the smoothness term needs head_out and grad_out", who); return 1; }
+    // the endpoint phase may not read an endpoint (its lanes update them): the pairs' gradients must arrive precomputed
+    if (!pl.smooth_pair_grads) { hgs_set_error("%s: a smoothness term needs HgsBlockPlan.smooth_pair_grads", who); return 1; }
+  }
+  if (pl.ep_adam.p && (!pl.ep_adam.m || !pl.ep_adam.v || !pl.ep_adam.coef)) { hgs_set_error("%s: incomplete Adam slot of the endpoints", who); return 1; }
+  return 0;
+}
 int hgs_backward_multi_params(void* stream, int P, int D, int M, int R, int W, int H, int flags, const float* bg7,
                               const float* means3D, const float* shs, const float* scales, const float* rotations,
                               const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
                               float tan_fovy, const int* radii, const void* geom_buf, const void* binning_buf, const void* image_buf,
                               const float* const* dL_dpix_planes7, void* scratch, float* dL_dsh, const HgsParamBackward* pb) {
+  return hgs_backward_multi_params_planned(stream, P, D, M, R, W, H, flags, bg7, means3D, shs, scales, rotations, viewmatrix,
+                                           projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buf, binning_buf, image_buf,
+                                           dL_dpix_planes7, scratch, dL_dsh, pb, nullptr);
+}
+int hgs_backward_multi_params_planned(void* stream, int P, int D, int M, int R, int W, int H, int flags, const float* bg7,
+                                      const float* means3D, const float* shs, const float* scales, const float* rotations,
+                                      const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                                      float tan_fovy, const int* radii, const void* geom_buf, const void* binning_buf,
+                                      const void* image_buf, const float* const* dL_dpix_planes7, void* scratch, float* dL_dsh,
+                                      const HgsParamBackward* pb, const HgsBlockPlan* plan) {
   if (!pb || (pb->kind != HGS_PARAMS_HAIR && pb->kind != HGS_PARAMS_CLOUD)) { hgs_set_error("hgs_backward_multi_params: params->kind must be HGS_PARAMS_HAIR or HGS_PARAMS_CLOUD"); return 1; }
+  if (plan && P == 0) { hgs_set_error("hgs_backward_multi_params_planned: a block plan needs a launch (P > 0)"); return 1; }
+  if (plan && check_block_plan(*plan, P, *pb)) return 1;
   if (P == 0 && pb->head_tail.out) { hgs_set_error("hgs_backward_multi_params: a deferred loss-head tail needs a launch (P > 0)"); return 1; }
   if (P == 0) return 0;
   if (!shs || !scales || !rotations || !dL_dsh) { hgs_set_error("hgs_backward_multi_params: SH colours and (scales, rotations) are required"); return 1; }
@@ -387,10 +430,11 @@ int hgs_backward_multi_params(void* stream, int P, int D, int M, int R, int W, i
     return 1;
   }
   if (pb->kind == HGS_PARAMS_HAIR) {
-    if (!pb->endpoints || !pb->endpoint_pairs || !pb->seg_contrib || !pb->d_width || ((size_t)pb->seg_contrib & 15)) {
+    // (with a block plan the contributions stay in LDS and the tail rides here: there is no gather launch)
+    if (!pb->endpoints || !pb->endpoint_pairs || (!plan && !pb->seg_contrib) || !pb->d_width || ((size_t)pb->seg_contrib & 15)) {
       hgs_set_error("hgs_backward_multi_params: null (or, seg_contrib, unaligned) hair argument"); return 1;
     }
-    if (pb->head_tail.out) { hgs_set_error("hgs_backward_multi_params: the strand model's deferred tail rides in hgs_hair_endpoint_gather"); return 1; }
+    if (!plan && pb->head_tail.out) { hgs_set_error("hgs_backward_multi_params: the strand model's deferred tail rides in hgs_hair_endpoint_gather"); return 1; }
   } else if (!pb->rotation_raw || !pb->d_means3D || !pb->d_scaling_raw || !pb->d_rotation_raw || ((size_t)pb->rotation_raw & 15) ||
              ((size_t)pb->d_rotation_raw & 15)) {
     hgs_set_error("hgs_backward_multi_params: null (or, rotation_raw / d_rotation_raw, unaligned) cloud argument"); return 1;
@@ -399,7 +443,7 @@ int hgs_backward_multi_params(void* stream, int P, int D, int M, int R, int W, i
   HgsParamBackward p = *pb;
   return backward_impl(stream, P, D, M, R, W, H, 4, flags, bg7, means3D, shs, nullptr, scales, 1.f, rotations, nullptr, viewmatrix,
                        projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buf, binning_buf, image_buf, dL_dpix_planes7, scratch,
-                       nullptr, p.dL_dmeans2D_rgb, nullptr, nullptr, nullptr, nullptr, nullptr, dL_dsh, nullptr, nullptr, &p);
+                       nullptr, p.dL_dmeans2D_rgb, nullptr, nullptr, nullptr, nullptr, nullptr, dL_dsh, nullptr, nullptr, &p, plan);
 }
 
 int hgs_backward(void* stream, int P, int D, int M, int R, int W, int H, int n_extra, int flags, const float* bg,

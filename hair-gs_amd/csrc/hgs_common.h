@@ -351,7 +351,8 @@ static inline size_t hgs_row_reduce_floats(size_t P, size_t R) { return P * 16 +
 int hgs_launch_row_reduce(hipStream_t s, int P, int Rcap, const float* inst_grad, const uint32_t* status, float* row_sums,
                           float* row_partials);
 int hgs_launch_preprocess_bwd(hipStream_t s, const HgsBwdArgs& a, const HgsGeom& g, const HgsBinning& b,
-                              const float* inst_grad, int Rcap, const uint32_t* status, const HgsParamBackward* pb = nullptr);
+                              const float* inst_grad, int Rcap, const uint32_t* status, const HgsParamBackward* pb = nullptr,
+                              const HgsBlockPlan* plan = nullptr);
 int hgs_launch_mark_visible(hipStream_t s, int P, const float* means3D, const float* viewmatrix, uint8_t* present);
 int hgs_launch_dist2(hipStream_t s, int P, const float* points, float* out, void* scratch, size_t scratch_bytes);
 size_t hgs_dist2_scratch(int P);

@@ -1066,7 +1066,18 @@ __global__ __launch_bounds__(HGS_BLOCK) void row_reduce_kernel(const float4* __r
 //           lane -- cloud_bwd_kernel's launch is gone; the loss head's deferred tail rides in one spare workgroup here.
 // The parameter arithmetic is the shared device code of hgs_strand_bwd.h, evaluated without contraction in both translation
 // units: the fused backward's results are the two-launch form's bit for bit (tests/test_gpu_train.py).
-template <bool DC_ONLY, int MODE>
+// PLAN (MODE 1 only; include/hgs.h HgsBlockPlan, hgs_backward_multi_params_planned): the workgroups own whole strands --
+// workgroup c maps lane t to segment s0[c] + t (a dead lane when t >= ns[c]: such lanes occur in EVERY workgroup, take part in
+// the wave-wide row code with zero rows and store nothing) -- so both segments of an endpoint are lanes of ONE workgroup.  Their
+// contributions go to LDS instead of seg_contrib, and behind one barrier lane t < ne[c] is the gather launch's endpoint lane for
+// endpoint ep_list[e0[c] + t] (hgs_endpoint_sum, d_endpoints, the endpoint's Adam update): strand_gather_kernel's launch is gone.
+// The barrier also puts every read of an endpoint (seg_pre, at the top of the lanes of the same workgroup) in front of its
+// update; nothing behind it reads one.  No workgroup waits for another.
+// The endpoint phase is the gather's arithmetic in the gather's order: the same bits, GIVEN the same row sums.  Those are the
+// unplanned form's bits with row_reduce_kernel's sums (a.row_sums) and in the in-lane loop; a wavefront that streams
+// (hgs_stream_rows, above: the association depends on where a Gaussian's rows fall in its wavefront's run) holds other
+// segments here than there, and may stream here and not there: same terms, other association, fixed for a given pass.
+template <bool DC_ONLY, int MODE, bool PLAN = false>
 // (five waves per SIMD: 87 VGPRs; at six the compiler spills six registers and the kernel takes 11.7 instead of 8.9 us)
 #ifndef HGS_PPB_WAVES
 #define HGS_PPB_WAVES 5
@@ -1074,18 +1085,27 @@ template <bool DC_ONLY, int MODE>
 // (MODE 1 / 2 with view-dependent SH: 116 VGPRs, four waves per SIMD; the DC-only forms fit five: 88 / 86)
 __global__ __launch_bounds__(HGS_BLOCK) __attribute__((amdgpu_waves_per_eu((MODE == 0 || DC_ONLY) ? HGS_PPB_WAVES : HGS_PPB_WAVES - 1))) void preprocess_bwd_kernel(HgsBwdArgs a, HgsGeom g, HgsBinning b,
                                                                    const float* __restrict__ inst_grad, uint32_t Rcap,
-                                                                   const uint32_t* __restrict__ status, HgsParamBackward pb) {
+                                                                   const uint32_t* __restrict__ status, HgsParamBackward pb,
+                                                                   HgsBlockPlan pl) {
+  static_assert(!PLAN || MODE == 1, "a block plan belongs to the strand form");
   __shared__ float4 s_acc[HGS_BLOCK / 64][64][4];     // hgs_stream_rows: per wavefront, one accumulator row per lane
   __shared__ uint32_t s_head[HGS_BLOCK / 64][16];
-  if ((int)(blockIdx.x * HGS_BLOCK) >= a.P) {
+  if (PLAN ? (int)blockIdx.x >= pl.n_chunks : (int)(blockIdx.x * HGS_BLOCK) >= a.P) {
     // (the loss head's deferred tail: the spare workgroup behind the launch's own, all of whose lanes are past P)
     if (MODE != 0 && pb.head_tail.out && blockIdx.x == gridDim.x - 1) hgs_head_tail_block(pb.head_tail);
     return;
   }
-  // (lanes past P of the last workgroup stay: the row summation below is a wavefront-wide operation; they read Gaussian P - 1
-  // and leave before anything is stored)
-  const bool live = (int)(blockIdx.x * HGS_BLOCK + threadIdx.x) < a.P;
-  const int idx = live ? (int)(blockIdx.x * HGS_BLOCK + threadIdx.x) : a.P - 1;
+  // PLAN: this workgroup's chunk (wave-uniform), clamped to the model's sizes -- whatever the table holds, no lane leaves them
+  int ck_s0 = 0, ck_ns = 0, ck_e0 = 0, ck_ne = 0;
+  if (PLAN) {
+    const int4 ck = ((const int4*)pl.chunks)[blockIdx.x];
+    ck_s0 = min(max(ck.x, 0), a.P - 1); ck_ns = min(max(ck.y, 0), min(HGS_BLOCK, a.P - ck_s0));
+    ck_e0 = min(max(ck.z, 0), pl.n_endpoints); ck_ne = min(max(ck.w, 0), min(HGS_BLOCK, pl.n_endpoints - ck_e0));
+  }
+  // (lanes past P of the last workgroup -- PLAN: past the chunk's segments -- stay: the row summation below is a wavefront-wide
+  // operation; they read a Gaussian of their workgroup's and store nothing)
+  const bool live = PLAN ? (int)threadIdx.x < ck_ns : (int)(blockIdx.x * HGS_BLOCK + threadIdx.x) < a.P;
+  const int idx = PLAN ? ck_s0 + (live ? (int)threadIdx.x : 0) : (live ? (int)(blockIdx.x * HGS_BLOCK + threadIdx.x) : a.P - 1);
   const int D = DC_ONLY ? 0 : a.D;
   // A forward that overflowed its binning capacity (status[1]) dropped instances: their rows of the scratch were never
   // written.  Such a pass is void; its backward returns EXACTLY ZERO for every gradient (deterministic, finite) and the
@@ -1140,6 +1160,12 @@ __global__ __launch_bounds__(HGS_BLOCK) __attribute__((amdgpu_waves_per_eu((MODE
   if (MODE == 1) seg_pre = hgs_segment_geom(idx, pb.endpoints, pb.endpoint_pairs);
   if (MODE == 2) raw_rot_pre = ((const float4*)pb.rotation_raw)[idx];
   if (MODE != 0) mask_pre = pb.extra4[4 * (size_t)idx];
+  // (PLAN: the endpoint lane's id alone -- its adjacency codes and pair gradients, 22 registers, are requested behind the
+  // Gaussian's arithmetic: held across it they cost the DC-only form a scratch segment)
+  const bool ep_live = PLAN && (int)threadIdx.x < ck_ne;
+  const bool ep_with_pairs = PLAN && pl.ep_pairs && pl.n_smooth > 0;
+  int ep_id = 0;
+  if (PLAN && ep_live) ep_id = min(max(pl.ep_list[ck_e0 + (int)threadIdx.x], 0), pl.n_endpoints - 1);
   {
     // ---- deterministic gather of this Gaussian's per-instance partial sums (instance order = tile rect order)
     const HgsRect rc = rc_pre;
@@ -1405,11 +1431,11 @@ __global__ __launch_bounds__(HGS_BLOCK) __attribute__((amdgpu_waves_per_eu((MODE
                 4 * z * (D_(1, 1) + D_(0, 0));
 #undef D_
     }
-  } else if (a.shs) {
+  } else if (a.shs && live) {   // (live: a dead lane shares its idx with a live one, whose dL_dsh it must not clear)
     float* dsh = a.dL_dsh + (size_t)idx * M * 3;
     for (int k = 0; k < 3 * M; k++) dsh[k] = 0.f;
   }
-  if (!live) return;
+  if (!PLAN && !live) return;   // (PLAN: dead lanes stay up to the barrier below, and may be endpoint lanes behind it)
   // every output is written (zeros for culled Gaussians): no separate zero-fill pass
   // returned screen-space gradient: in the single-pass mode the RGB channels' share only (what the reference's
   // densification statistics read from the RGB pass); dL_dmeans3D above used the total
@@ -1430,35 +1456,74 @@ __global__ __launch_bounds__(HGS_BLOCK) __attribute__((amdgpu_waves_per_eu((MODE
     return;
   }
   // ---- MODE 1 / 2: the parameters' backward of this Gaussian, from registers (see the kernel's header)
-  if (a.dL_dmeans2D) { a.dL_dmeans2D[3 * idx] = gm2x; a.dL_dmeans2D[3 * idx + 1] = gm2y; a.dL_dmeans2D[3 * idx + 2] = 0.f; }
-  if (pb.max_radii2D) hgs_densify_stats_lane(idx, radius_pre, gm2x, gm2y, pb.max_radii2D, pb.grad_accum, pb.denom);
+  if (!PLAN || live) {
+    if (a.dL_dmeans2D) { a.dL_dmeans2D[3 * idx] = gm2x; a.dL_dmeans2D[3 * idx + 1] = gm2y; a.dL_dmeans2D[3 * idx + 2] = 0.f; }
+    if (pb.max_radii2D) hgs_densify_stats_lane(idx, radius_pre, gm2x, gm2y, pb.max_radii2D, pb.grad_accum, pb.denom);
+  }
   // (the forward's opacity, conic_opacity.w, exists for visible Gaussians only; an invisible one has dop = 0)
   const float o_act = vis ? co_pre.w : 0.f;
   if (MODE == 1) {
-    HgsSegGradVals gv;
-    gv.gx[0] = dmean[0]; gv.gx[1] = dmean[1]; gv.gx[2] = dmean[2];
-    gv.gs0 = dscale[0];
-    gv.gq = make_float4(drot[0], drot[1], drot[2], drot[3]);
-    gv.gd[0] = gv.gd[1] = gv.gd[2] = 0.f;
-    gv.ge = make_float4(dex[0], dex[1], dex[2], dex[3]);
-    gv.has_quat = true; gv.has_extra = true; gv.has_scale = true;
-    float h[3], gD[3];
-    hgs_segment_endpoint_grads_v(seg_pre, pb.dist_to_scale_factor, gv, h, gD);
-    float4* sc = (float4*)pb.seg_contrib + 2 * (size_t)idx;
-    sc[0] = make_float4(h[0] - gD[0], h[1] - gD[1], h[2] - gD[2], 0.f);
-    sc[1] = make_float4(h[0] + gD[0], h[1] + gD[1], h[2] + gD[2], 0.f);
-    const float g_w = (dscale[1] + dscale[2]) * s_pre[1];            // scale.y = exp(width): the forward's own value
-    const float g_o = dop * o_act * (1.f - o_act);                   // sigmoid'
-    const float g_m = dex[0] * mask_pre * (1.f - mask_pre);
-    pb.d_width[idx] = g_w;
-    pb.d_opacity_raw[idx] = g_o;
-    pb.d_mask_raw[idx] = g_m;
-    // Adam in the lane (include/hgs.h HgsAdamSlot): every gradient of this Gaussian's own parameters is final here, and nothing
-    // else in the launch reads the raw parameters (the lane itself works on the forward's activations)
-    hgs_adam_lane<1>(pb.adam.slot[0], (size_t)idx, &g_w, pb.adam.beta1, pb.adam.beta2, pb.adam.eps);
-    hgs_adam_lane<1>(pb.adam.slot[1], (size_t)idx, &g_o, pb.adam.beta1, pb.adam.beta2, pb.adam.eps);
-    hgs_adam_lane<1>(pb.adam.slot[2], (size_t)idx, &g_m, pb.adam.beta1, pb.adam.beta2, pb.adam.eps);
-    hgs_adam_lane<3>(pb.adam.slot[3], (size_t)idx, dsh_dc, pb.adam.beta1, pb.adam.beta2, pb.adam.eps);
+    // (PLAN: the endpoint lane's adjacency codes and the pair gradients they name, requested in front of the segment's own
+    // stores and updates, whose round trips cover them)
+    int2 ep_cs = make_int2(-1, -1);
+    int4 ep_cp = make_int4(-1, -1, -1, -1);
+    float4 ep_u[4] = {};
+    if (PLAN && ep_live) {
+      ep_cs = *(const int2*)(pl.ep_segments + 2 * (size_t)ep_id);
+      if (ep_with_pairs) ep_cp = *(const int4*)(pl.ep_pairs + 4 * (size_t)ep_id);
+    }
+    if (PLAN && ep_live && ep_with_pairs) {
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        const int code[4] = {ep_cp.x, ep_cp.y, ep_cp.z, ep_cp.w};
+        const int c = min(max(code[s], 0), 4 * pl.n_smooth - 1);
+        ep_u[s] = ((const float4*)pl.smooth_pair_grads)[2 * (size_t)(c >> 2) + ((c & 3) >> 1)];
+      }
+    }
+    if (!PLAN || live) {
+      HgsSegGradVals gv;
+      gv.gx[0] = dmean[0]; gv.gx[1] = dmean[1]; gv.gx[2] = dmean[2];
+      gv.gs0 = dscale[0];
+      gv.gq = make_float4(drot[0], drot[1], drot[2], drot[3]);
+      gv.gd[0] = gv.gd[1] = gv.gd[2] = 0.f;
+      gv.ge = make_float4(dex[0], dex[1], dex[2], dex[3]);
+      gv.has_quat = true; gv.has_extra = true; gv.has_scale = true;
+      float h[3], gD[3];
+      hgs_segment_endpoint_grads_v(seg_pre, pb.dist_to_scale_factor, gv, h, gD);
+      // (PLAN: to the lane's own accumulator row of LDS, which its wavefront's row phase has left -- no other wavefront touches
+      // it before the barrier)
+      float4* sc = PLAN ? &s_acc[threadIdx.x >> 6][threadIdx.x & 63][0] : (float4*)pb.seg_contrib + 2 * (size_t)idx;
+      sc[0] = make_float4(h[0] - gD[0], h[1] - gD[1], h[2] - gD[2], 0.f);
+      sc[1] = make_float4(h[0] + gD[0], h[1] + gD[1], h[2] + gD[2], 0.f);
+      const float g_w = (dscale[1] + dscale[2]) * s_pre[1];            // scale.y = exp(width): the forward's own value
+      const float g_o = dop * o_act * (1.f - o_act);                   // sigmoid'
+      const float g_m = dex[0] * mask_pre * (1.f - mask_pre);
+      pb.d_width[idx] = g_w;
+      pb.d_opacity_raw[idx] = g_o;
+      pb.d_mask_raw[idx] = g_m;
+      // Adam in the lane (include/hgs.h HgsAdamSlot): every gradient of this Gaussian's own parameters is final here, and nothing
+      // else in the launch reads the raw parameters (the lane itself works on the forward's activations)
+      hgs_adam_lane<1>(pb.adam.slot[0], (size_t)idx, &g_w, pb.adam.beta1, pb.adam.beta2, pb.adam.eps);
+      hgs_adam_lane<1>(pb.adam.slot[1], (size_t)idx, &g_o, pb.adam.beta1, pb.adam.beta2, pb.adam.eps);
+      hgs_adam_lane<1>(pb.adam.slot[2], (size_t)idx, &g_m, pb.adam.beta1, pb.adam.beta2, pb.adam.eps);
+      hgs_adam_lane<3>(pb.adam.slot[3], (size_t)idx, dsh_dc, pb.adam.beta1, pb.adam.beta2, pb.adam.eps);
+    }
+    if (PLAN) {
+      // ---- the endpoint phase: every lane of the workgroup arrives here, whatever it was above
+      __syncthreads();
+      if (!ep_live) return;
+      const int cs[2] = {ep_cs.x, ep_cs.y}, cp[4] = {ep_cp.x, ep_cp.y, ep_cp.z, ep_cp.w};
+      float4 ct[2];
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const int ls = min(max((cs[s] >> 1) - ck_s0, 0), HGS_BLOCK - 1);   // the segment's lane in this workgroup
+        ct[s] = s_acc[ls >> 6][ls & 63][cs[s] & 1];
+      }
+      float acc[3];
+      hgs_endpoint_sum(cs, ct, cp, ep_u, ep_with_pairs, hgs_smooth_scale(ep_with_pairs ? pl.n_smooth : 0, pl.head_out, pl.grad_out), acc);
+      pl.d_endpoints[3 * (size_t)ep_id] = acc[0]; pl.d_endpoints[3 * (size_t)ep_id + 1] = acc[1]; pl.d_endpoints[3 * (size_t)ep_id + 2] = acc[2];
+      hgs_adam_lane<3>(pl.ep_adam, (size_t)ep_id, acc, pl.beta1, pl.beta2, pl.eps);
+    }
   } else {
     const HgsCloudParamGrads cg = hgs_cloud_param_grads(s_pre[0], s_pre[1], s_pre[2], raw_rot_pre, o_act, mask_pre, dscale,
                                                         make_float4(drot[0], drot[1], drot[2], drot[3]), dop,
@@ -1559,16 +1624,20 @@ int hgs_launch_row_reduce(hipStream_t s, int P, int Rcap, const float* inst_grad
   return 0;
 }
 int hgs_launch_preprocess_bwd(hipStream_t s, const HgsBwdArgs& a, const HgsGeom& g, const HgsBinning& b,
-                              const float* inst_grad, int Rcap, const uint32_t* status, const HgsParamBackward* pb) {
+                              const float* inst_grad, int Rcap, const uint32_t* status, const HgsParamBackward* pb,
+                              const HgsBlockPlan* plan) {
   const int mode = pb ? pb->kind : 0;
   const HgsParamBackward p = pb ? *pb : HgsParamBackward{};
-  // (the loss head's deferred tail, MODE 1 / 2: one spare workgroup behind the launch's own)
-  const int nblk = (a.P + HGS_BLOCK - 1) / HGS_BLOCK + ((mode != 0 && p.head_tail.out) ? 1 : 0);
+  if (plan && mode != HGS_PARAMS_HAIR) { hgs_set_error("a block plan belongs to the strand model's parameter backward"); return 1; }
+  const HgsBlockPlan pl = plan ? *plan : HgsBlockPlan{};
+  // (the loss head's deferred tail, MODE 1 / 2: one spare workgroup behind the launch's own; with a plan: one workgroup per chunk)
+  const int nblk = (plan ? pl.n_chunks : (a.P + HGS_BLOCK - 1) / HGS_BLOCK) + ((mode != 0 && p.head_tail.out) ? 1 : 0);
   const bool dc = !a.shs || (a.D == 0 && a.M == 1);
   {
     HgsProfScope _prof(s, HGS_K_PREPROCESS_BWD);
-#define HGS_PPB_LAUNCH(DC, MODE) hipLaunchKernelGGL((preprocess_bwd_kernel<DC, MODE>), dim3(nblk), dim3(HGS_BLOCK), 0, s, a, g, b, inst_grad, (uint32_t)Rcap, status, p)
+#define HGS_PPB_LAUNCH(...) hipLaunchKernelGGL((preprocess_bwd_kernel<__VA_ARGS__>), dim3(nblk), dim3(HGS_BLOCK), 0, s, a, g, b, inst_grad, (uint32_t)Rcap, status, p, pl)
     if (mode == 0) { if (dc) HGS_PPB_LAUNCH(true, 0); else HGS_PPB_LAUNCH(false, 0); }
+    else if (plan) { if (dc) HGS_PPB_LAUNCH(true, 1, true); else HGS_PPB_LAUNCH(false, 1, true); }
     else if (mode == HGS_PARAMS_HAIR) { if (dc) HGS_PPB_LAUNCH(true, 1); else HGS_PPB_LAUNCH(false, 1); }
     else { if (dc) HGS_PPB_LAUNCH(true, 2); else HGS_PPB_LAUNCH(false, 2); }
 #undef HGS_PPB_LAUNCH

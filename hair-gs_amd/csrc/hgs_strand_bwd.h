@@ -115,6 +115,34 @@ __device__ __forceinline__ HgsCloudParamGrads hgs_cloud_param_grads(float s0, fl
   return out;
 }
 
+// What an endpoint sums when everything arrives precomputed: the contributions ct[s] of its (<= 2) segments (code cs[s] = 2 *
+// segment + end, < 0: none), then its (<= 4) smoothness pair roles (code cp[s] = 4 * pair + role, < 0: none; u[s] = the role's
+// unit gradient and ok flag, HgsStrandFusion.smooth_pair_grads; with_pairs false: no smoothness term), in that order.  Absent
+// slots carry item 0's values and are masked out here.  Shared by the gather launch (strand_gather_kernel) and the endpoint
+// phase of the planned preprocess backward (hgs_preprocess.hip); no contraction, as above: the same bits in both.
+__device__ __forceinline__ void hgs_endpoint_sum(const int* cs, const float4* ct, const int* cp, const float4* u, bool with_pairs,
+                                                 float smooth_scale, float* acc) {
+#pragma clang fp contract(off)
+  acc[0] = acc[1] = acc[2] = 0.f;
+#pragma unroll
+  for (int s = 0; s < 2; s++)
+    if (cs[s] >= 0) { acc[0] += ct[s].x; acc[1] += ct[s].y; acc[2] += ct[s].z; }
+  if (!with_pairs) return;
+#pragma unroll
+  for (int s = 0; s < 4; s++) {
+    const float pg[3] = {smooth_scale * u[s].x, smooth_scale * u[s].y, smooth_scale * u[s].z};   // as hgs_smooth_pair_grads forms it
+    const float sign = (cp[s] & 1) ? 1.f : -1.f;               // a0: -g0, a1: +g0, b0: -g1, b1: +g1
+    if (u[s].w != 0.f && cp[s] >= 0) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) acc[c] += sign * pg[c];
+    }
+  }
+}
+// the scale of the smoothness gradient (include/hgs.h HgsStrandFusion): wave-uniform, 0 without the term
+__device__ __forceinline__ float hgs_smooth_scale(int n_smooth, const float* head_out, const float* grad_out) {
+  return n_smooth > 0 ? head_out[HGS_HEAD_G_SMOOTH] * grad_out[0] / fmaxf(head_out[HGS_HEAD_SMOOTH_COUNT], 1.f) : 0.f;
+}
+
 struct HgsStrandBwdArgs {
   int P; const float* ep; const long long* pairs; const float* width; float f;
   const float* g_xyz; const float* g_scale; const float* g_quat; const float* g_dir;
@@ -145,8 +173,7 @@ __device__ __forceinline__ void hgs_strand_bwd_block(const HgsStrandBwdArgs& A_i
   if (fu.head_tail.out && blk == nblk - 1) { hgs_head_tail_block(fu.head_tail); return; }
   const int nb_seg = CONTRIB ? 0 : (P + 255) / 256;
   const HgsSegGrads sg = {A.g_xyz, A.g_scale, A.g_quat, A.g_dir, A.g_extra4};
-  const float smooth_scale = fu.n_smooth > 0
-      ? fu.head_out[HGS_HEAD_G_SMOOTH] * fu.grad_out[0] / fmaxf(fu.head_out[HGS_HEAD_SMOOTH_COUNT], 1.f) : 0.f;
+  const float smooth_scale = hgs_smooth_scale(fu.n_smooth, fu.head_out, fu.grad_out);
   if ((int)blk >= nb_seg) {
     const int i = ((int)blk - nb_seg) * 256 + threadIdx.x;
     if (fu.ep_segments) {
@@ -164,30 +191,36 @@ __device__ __forceinline__ void hgs_strand_bwd_block(const HgsStrandBwdArgs& A_i
       int4 cp = make_int4(-1, -1, -1, -1);
       if (with_smooth) cp = *(const int4*)(fu.ep_pairs + 4 * (size_t)ic);
       const int seg_code[2] = {cs.x, cs.y};
+      const int pair_code[4] = {cp.x, cp.y, cp.z, cp.w};
+      if (CONTRIB && (!with_smooth || fu.smooth_pair_grads)) {
+        // everything arrives precomputed (hgs_endpoint_sum): the pairs' unit gradients as the forward's spare workgroups left
+        // them (HgsStrandFusion.smooth_pair_grads: the role's 16 bytes instead of pair -> index row -> four endpoints), the
+        // segments' contributions as the rasterizer backward left them; nothing here reads an endpoint
+        float4 u[4] = {}, ct[2];
+        if (with_smooth) {
+#pragma unroll
+          for (int s = 0; s < 4; s++) {
+            const int code = pair_code[s] >= 0 ? pair_code[s] : 0;
+            u[s] = ((const float4*)fu.smooth_pair_grads)[2 * (size_t)(code >> 2) + ((code & 3) >> 1)];
+          }
+        }
+#pragma unroll
+        for (int s = 0; s < 2; s++) ct[s] = A.seg_contrib[seg_code[s] >= 0 ? seg_code[s] : 0];
+        hgs_endpoint_sum(seg_code, ct, pair_code, u, with_smooth, smooth_scale, acc);
+        A.d_ep[3 * (size_t)i] = acc[0]; A.d_ep[3 * (size_t)i + 1] = acc[1]; A.d_ep[3 * (size_t)i + 2] = acc[2];
+        // Adam in the lane (include/hgs.h HgsAdamSlot): possible because nothing of this launch reads the endpoints -- (round 4
+        // still noted that the neighbouring lanes re-read them)
+        hgs_adam_lane<3>(A.adam.slot[0], (size_t)i, acc, A.adam.beta1, A.adam.beta2, A.adam.eps);
+        return;
+      }
       HgsSegGeom geo[2] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
       if (!CONTRIB) {
 #pragma unroll
         for (int s = 0; s < 2; s++) geo[s] = hgs_segment_geom(seg_code[s] >= 0 ? seg_code[s] >> 1 : 0, ep, pairs);
       }
-      const int pair_code[4] = {cp.x, cp.y, cp.z, cp.w};
       float pg0[4][3], pg1[4][3];
       bool pok[4] = {false, false, false, false};
-      if (CONTRIB && with_smooth && fu.smooth_pair_grads) {
-        // the pairs' unit gradients as the forward's spare workgroups left them (HgsStrandFusion.smooth_pair_grads): the role's
-        // 16 bytes instead of pair -> index row -> four endpoints; times the scale, as hgs_smooth_pair_grads forms it
-        float4 u[4];
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-          const int code = pair_code[s] >= 0 ? pair_code[s] : 0;
-          u[s] = ((const float4*)fu.smooth_pair_grads)[2 * (size_t)(code >> 2) + ((code & 3) >> 1)];
-        }
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-          pok[s] = u[s].w != 0.f && pair_code[s] >= 0;
-          pg0[s][0] = pg1[s][0] = smooth_scale * u[s].x; pg0[s][1] = pg1[s][1] = smooth_scale * u[s].y;
-          pg0[s][2] = pg1[s][2] = smooth_scale * u[s].z;
-        }
-      } else if (with_smooth) {
+      if (with_smooth) {
 #pragma unroll
         for (int s = 0; s < 4; s++)
           pok[s] = hgs_smooth_pair_grads(pair_code[s] >= 0 ? pair_code[s] >> 2 : 0, ep, fu.smooth_pairs, fu.cos_threshold, fu.eps,

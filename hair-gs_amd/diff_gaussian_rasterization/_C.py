@@ -381,9 +381,9 @@ def _scratch(nbytes, dev):
 
 def _backward(n_extra, background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
               projmatrix, tan_fovx, tan_fovy, planes, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug=False,
-              params=None):
+              params=None, plan=None):
     """hgs_backward of a pass with 3 + n_extra channels (`planes`: one [H,W] gradient tensor per channel), or with `params`
-    hgs_backward_multi_params.  Returns the gradients in hgs_backward's order -- dL_dextra (None for 3 channels), dL_dmeans2D,
+    hgs_backward_multi_params (with `plan`, a filled hgs_runtime.BlockPlan: hgs_backward_multi_params_planned).  Returns the gradients in hgs_backward's order -- dL_dextra (None for 3 channels), dL_dmeans2D,
     dL_dconic, dL_dopacity, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations --, or dL_dsh alone with
     `params`."""
     L = rt.lib()
@@ -420,11 +420,11 @@ def _backward(n_extra, background, means3D, radii, colors, scales, rotations, sc
                                     float(tan_fovy), rt.ptr(radii_), rt.ptr(geomBuffer), rt.ptr(binningBuffer),
                                     rt.ptr(imageBuffer), plane_ptrs, rt.ptr(scratch), *[rt.ptr(g) for g in grads]))
         else:
-            rt.check(L.hgs_backward_multi_params(rt.current_stream(), P, int(degree), M, int(R), W, H, flags, rt.ptr(bg_),
-                                                 rt.ptr(means3D), rt.ptr(sh_), rt.ptr(scales_), rt.ptr(rots_), rt.ptr(view_),
-                                                 rt.ptr(proj_), rt.ptr(cam_), float(tan_fovx), float(tan_fovy), rt.ptr(radii_),
-                                                 rt.ptr(geomBuffer), rt.ptr(binningBuffer), rt.ptr(imageBuffer), plane_ptrs,
-                                                 rt.ptr(scratch), rt.ptr(grads), C.byref(params)))
+            rt.check(L.hgs_backward_multi_params_planned(
+                rt.current_stream(), P, int(degree), M, int(R), W, H, flags, rt.ptr(bg_), rt.ptr(means3D), rt.ptr(sh_),
+                rt.ptr(scales_), rt.ptr(rots_), rt.ptr(view_), rt.ptr(proj_), rt.ptr(cam_), float(tan_fovx), float(tan_fovy),
+                rt.ptr(radii_), rt.ptr(geomBuffer), rt.ptr(binningBuffer), rt.ptr(imageBuffer), plane_ptrs, rt.ptr(scratch),
+                rt.ptr(grads), C.byref(params), None if plan is None else C.byref(plan)))
         if debug:
             torch.cuda.synchronize(dev)
     return grads
@@ -457,11 +457,12 @@ def rasterize_gaussians_multi_backward(background7, means3D, radii, colors, scal
 
 def rasterize_gaussians_multi_backward_params(background7, means3D, radii, scales, rotations, viewmatrix, projmatrix, tan_fovx,
                                               tan_fovy, grad_planes, sh, degree, campos, geomBuffer, R, binningBuffer,
-                                              imageBuffer, params):
+                                              imageBuffer, params, plan=None):
     """hgs_backward_multi_params: the single-pass backward whose per-Gaussian launch also applies the parameters' backward
-    (`params`: a filled hgs_runtime.ParamBackward; its output tensors are the caller's).  Returns dL_dsh [P,M,3]."""
+    (`params`: a filled hgs_runtime.ParamBackward; its output tensors are the caller's).  `plan` (a filled hgs_runtime.BlockPlan,
+    strand models): that launch is also the endpoint gather (hgs_backward_multi_params_planned).  Returns dL_dsh [P,M,3]."""
     return _backward(4, background7, means3D, radii, None, scales, rotations, 1.0, None, viewmatrix, projmatrix, tan_fovx,
-                     tan_fovy, grad_planes, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, params=params)
+                     tan_fovy, grad_planes, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, params=params, plan=plan)
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):

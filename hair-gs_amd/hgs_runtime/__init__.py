@@ -33,6 +33,9 @@ SIGNATURES = {
     "hgs_param_backward_bytes": (sz, []),
     "hgs_backward_multi_params": (ci, [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp,
                                        vp, vp, vp]),
+    "hgs_block_plan_bytes": (sz, []),
+    "hgs_backward_multi_params_planned": (ci, [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp,
+                                               vp, vp, vp, vp, vp]),
     "hgs_hair_endpoint_gather": (ci, [vp, ci, vp, vp, vp, vp, vp]),
     "hgs_mark_visible": (ci, [vp, ci, vp, vp, vp, vp]),
     "hgs_dist2_scratch_bytes": (sz, [ci]),
@@ -230,6 +233,13 @@ class ParamBackward(C.Structure):
                 ("grad_accum", vp), ("denom", vp), ("head_tail", HeadTail), ("adam", AdamInline)]
 
 
+class BlockPlan(C.Structure):
+    """include/hgs.h HgsBlockPlan."""
+    _fields_ = [("n_chunks", ci), ("chunks", vp), ("ep_list", vp), ("n_segments", ci), ("n_endpoints", ci), ("ep_segments", vp),
+                ("ep_pairs", vp), ("smooth_pair_grads", vp), ("n_smooth", ci), ("head_out", vp), ("grad_out", vp),
+                ("d_endpoints", vp), ("ep_adam", AdamSlot), ("beta1", cf), ("beta2", cf), ("eps", cf)]
+
+
 PARAMS_HAIR, PARAMS_CLOUD = 1, 2
 HEAD_SKIP_PIXELS, HEAD_SKIP_SMOOTH = 1, 2
 VIEW_QUEUE_MAX = 16   # include/hgs.h HGS_VIEW_QUEUE_MAX
@@ -269,7 +279,7 @@ def lib():
                            "rebuild with hgs_runtime.build()")
         for fn, st in (("hgs_view_targets_bytes", ViewTargets), ("hgs_head_params_bytes", HeadParams),
                        ("hgs_strand_fusion_bytes", StrandFusion), ("hgs_param_forward_bytes", ParamForward),
-                       ("hgs_param_backward_bytes", ParamBackward),
+                       ("hgs_param_backward_bytes", ParamBackward), ("hgs_block_plan_bytes", BlockPlan),
                        ("hgs_adam_prep_bytes", AdamPrep), ("hgs_adam_inline_bytes", AdamInline),
                        ("hgs_raster_model_bytes", RasterModel), ("hgs_carve_view_bytes", CarveView)):
             if getattr(L, fn)() != C.sizeof(st):

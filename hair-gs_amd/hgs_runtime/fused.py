@@ -353,6 +353,15 @@ class FusedAdam(torch.optim.Optimizer):
         self._plan = None      # _InlinePlan: the in-lane form of the update (include/hgs.h HgsAdamSlot)
         self._inline_done = False
 
+    def ticket_words(self, dev):
+        """The launch's per-tensor ticket words (zero between launches: the kernel wraps them).  Whoever captures step() into a
+        graph calls this BEFORE the capture: words created here during a capture live in the graph's pool and are zeroed by that
+        graph's replays alone -- a second graph captured after it (several steps per launch) that is replayed first would take
+        its tickets from whatever the pool block held, and advance no step counter."""
+        if self._tickets is None or self._tickets.device != dev:
+            self._tickets = torch.zeros(8, dtype=torch.int32, device=dev)
+        return self._tickets
+
     def inline_plan(self):
         """The plan of the in-lane update for the CURRENT parameter tensors (rebuilt when a tensor, a moment, a step counter or
         a learning-rate tensor has been replaced): device-resident HgsAdamPrep + coefficient table, slots per parameter."""
@@ -433,11 +442,9 @@ class FusedAdam(torch.optim.Optimizer):
             self._call = (key, n, arrs, numel)
         _, n, arrs, numel = self._call
         dev = rows[0][0].device
-        if self._tickets is None or self._tickets.device != dev:
-            self._tickets = torch.zeros(8, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
             rt.check(rt.lib().hgs_adam_step(rt.current_stream(), n, arrs[0], arrs[1], arrs[2], arrs[3], arrs[4], arrs[5],
-                                            numel, float(beta1), float(beta2), float(eps), self._tickets.data_ptr()))
+                                            numel, float(beta1), float(beta2), float(eps), self.ticket_words(dev).data_ptr()))
         # the kernel wrote the parameters through raw pointers: tell autograd that they changed in place
         for r in rows:
             torch.autograd.graph.increment_version(r[0])

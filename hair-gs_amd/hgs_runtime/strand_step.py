@@ -266,6 +266,66 @@ def _adjacency(member_ids, roles, n_targets, max_degree):
     return table.contiguous()
 
 
+BLOCK_PLAN_MAX = 256   # segments, and endpoints, of one chunk: the lanes of a workgroup (include/hgs.h HgsBlockPlan)
+
+
+def _block_plan(ep_segments, n_segments, limit=BLOCK_PLAN_MAX):
+    """The block plan of a strand model (include/hgs.h HgsBlockPlan) from its endpoint adjacency `ep_segments` ([E,2] codes
+    2 * segment + end, -1 = none): the segments cut into chunks [s0, s0 + ns) of consecutive segments in storage order that
+    own whole strands, each with the list of the endpoints whose segments it holds.  Returns (chunks int32 [C,4] = s0, ns, e0,
+    ne; ep_list int32 [E]: the chunks' endpoint ids, chunk after chunk) on the table's device, or None where no such
+    partition exists (a strand of more than limit - 1 segments, storage that is not strand-ordered): the iteration then keeps
+    its two launches.
+    A cut in front of segment b is allowed when no endpoint has one segment below b and another at or above b; from a cut the
+    next one is the furthest allowed cut within `limit` segments and `limit` endpoints.  Endpoints without a segment go to
+    the first chunks that have room.  (numpy on the host, at topology events only; the only Python loop walks the chunks.)"""
+    P, dev = int(n_segments), ep_segments.device
+    codes = ep_segments.detach().cpu().numpy().astype(np.int64)
+    E = codes.shape[0]
+    if P <= 0 or E <= 0:
+        return None
+    seg = codes >> 1
+    has = codes >= 0
+    if bool((has & (seg >= P)).any()):
+        return None
+    lo = np.where(has, seg, P).min(axis=1)              # (P: an endpoint without a segment)
+    hi = np.where(has, seg, -1).max(axis=1)
+    bound = hi >= 0
+    # cuts b in (lo, hi] of some endpoint are barred
+    barred = np.zeros(P + 2, dtype=np.int64)
+    np.add.at(barred, lo[bound] + 1, 1)
+    np.add.at(barred, hi[bound] + 1, -1)
+    barred = np.cumsum(barred)[:P + 1]
+    cuts = np.flatnonzero(barred == 0)                  # 0 and P among them
+    # endpoints (with a segment) whose segments lie below each cut: an endpoint counts from its lowest segment on
+    below = np.concatenate(([0], np.cumsum(np.bincount(lo[bound], minlength=P))))[cuts]
+    nxt = np.minimum(np.searchsorted(cuts, cuts + limit, side="right"), np.searchsorted(below, below + limit, side="right")) - 1
+    nxt, last = nxt.tolist(), len(cuts) - 1
+    chain, i = [0], 0
+    while i < last:
+        if nxt[i] <= i:
+            return None                                 # the strand behind this cut fits no chunk
+        i = nxt[i]
+        chain.append(i)
+    s0 = cuts[np.asarray(chain[:-1])]
+    ns = cuts[np.asarray(chain[1:])] - s0
+    ne = below[np.asarray(chain[1:])] - below[np.asarray(chain[:-1])]
+    chunk_of = np.full(E, -1, dtype=np.int64)
+    chunk_of[bound] = np.searchsorted(s0, lo[bound], side="right") - 1
+    loose = np.flatnonzero(~bound)
+    if loose.size:
+        room = np.cumsum(limit - ne)
+        if room[-1] < loose.size:
+            return None
+        take = np.searchsorted(room, np.arange(loose.size), side="right")
+        chunk_of[loose] = take
+        ne = ne + np.bincount(take, minlength=ne.size)
+    order = np.argsort(chunk_of, kind="stable")          # by chunk, then by endpoint id
+    e0 = np.concatenate(([0], np.cumsum(ne)[:-1]))
+    chunks = np.stack([s0, ns, e0, ne], axis=1).astype(np.int32)
+    return (torch.from_numpy(chunks).contiguous().to(dev), torch.from_numpy(order.astype(np.int32)).contiguous().to(dev))
+
+
 def head_params(H, W, opt, n_smooth, n_endpoints, min_val, has_float_mask, threshold_deg=30.0, eps=1e-6):
     p = rt.HeadParams()
     p.H, p.W = int(H), int(W)
@@ -329,8 +389,9 @@ def _raster_head_forward(step, xyz, scale, quat, opacity, extra4, shs, endpoints
 
 
 def _head_raster_backward(ctx, step, go, xyz, scale, quat, shs, planes, radii, geom, binning, img, scratch, out, endpoints,
-                          d_ep, n_endpoints, params=None):
-    """Loss-head backward + single-pass rasterizer backward; returns (grad_out tensor, rasterizer gradients)."""
+                          d_ep, n_endpoints, params=None, plan=None):
+    """Loss-head backward + single-pass rasterizer backward; returns (grad_out tensor, rasterizer gradients).  `plan`: the
+    rt.BlockPlan that goes with `params` (a strand model whose parameter launch is the endpoint gather too), or None."""
     from diff_gaussian_rasterization import _C as raster
     g, vt, hp, L = step.gaussians, step.views, step.head, rt.lib()
     dev = xyz.device
@@ -363,7 +424,7 @@ def _head_raster_backward(ctx, step, go, xyz, scale, quat, shs, planes, radii, g
         params.dL_dmeans2D_rgb = rt.ptr(g_means2D)
         g_sh = raster.rasterize_gaussians_multi_backward_params(
             step.bg7_backward, xyz, radii, scale, quat, vt.viewmatrix, vt.projmatrix, vt.tanfovx, vt.tanfovy, grad_planes, shs,
-            g.active_sh_degree, vt.campos, geom, ctx.R, binning, img, params)
+            g.active_sh_degree, vt.campos, geom, ctx.R, binning, img, params, plan=plan)
         return go, (g_means2D, None, None, None, g_sh, None, None)
     empty = step.empty
     (g_means2D, _gc, g_ex, g_opac, g_means3D, _gcov, g_sh, g_scales, g_rot) = raster.rasterize_gaussians_multi_backward(
@@ -500,7 +561,18 @@ class _StrandIteration(torch.autograd.Function):
         if gather and step.fuse_param_backward and P > 0:
             # ---- round 5: the segment geometry's backward in the rasterizer backward's own lanes, then the endpoint gather
             pb = rt.ParamBackward()
-            seg_contrib = torch.empty((P, 2, 4), **f32)
+            # the topology's block plan (refresh()): the per-Gaussian launch is the endpoint gather too, its workgroups own whole
+            # strands (include/hgs.h HgsBlockPlan); its endpoint lanes read no endpoint, so the pairs' gradients must be there.
+            # Two quiet ways back to the two launches: the switch (fuse_endpoint_gather, the measurements' A/B aid), and a smoothness
+            # term whose pair gradients the forward did not leave (fuse_param_backward switched on between forward and backward).
+            # Either is the same arithmetic in the same order EXCEPT for the row sums of wavefronts that stream their rows (a
+            # Gaussian with more than 32 instances, rows summed in the launch): the plan groups other segments into a wavefront,
+            # so those sums associate differently (include/hgs.h hgs_backward_multi_params_planned) -- rounding, reproducible.
+            blocks = step.block_plan if step.fuse_endpoint_gather else None
+            smooth_adj = ctx.fused_smooth and step.ep_pairs is not None
+            if blocks is not None and smooth_adj and ctx.pair_grads is None:
+                blocks = None
+            seg_contrib = torch.empty((P, 2, 4), **f32) if blocks is None else None
             pb.kind, pb.endpoints, pb.endpoint_pairs = rt.PARAMS_HAIR, rt.ptr(endpoints), rt.ptr(pairs)
             pb.dist_to_scale_factor = float(g.dist_to_scale_factor)
             pb.seg_contrib, pb.d_width, pb.extra4 = rt.ptr(seg_contrib), rt.ptr(d_w), rt.ptr(extra4)
@@ -512,6 +584,29 @@ class _StrandIteration(torch.autograd.Function):
                 plan.fill(pb.adam, (g._width, g._opacity, g._mask, g._features_dc))
                 ep_adam = rt.AdamInline()
                 plan.fill(ep_adam, (g._endpoints,))
+            if blocks is not None:
+                # (the upstream gradient as _head_raster_backward will form it: a no-op on what backward() hands in)
+                go_t = None if go is None else go.contiguous().to(torch.float32)
+                bp = rt.BlockPlan()
+                bp.n_chunks, bp.chunks, bp.ep_list = int(blocks[0].shape[0]), blocks[0].data_ptr(), blocks[1].data_ptr()
+                bp.n_segments, bp.n_endpoints = P, E
+                bp.ep_segments = step.ep_segments.data_ptr()
+                if smooth_adj:
+                    bp.ep_pairs, bp.smooth_pair_grads = step.ep_pairs.data_ptr(), ctx.pair_grads.data_ptr()
+                    bp.n_smooth, bp.head_out, bp.grad_out = int(step.smooth_pairs.shape[0]), out.data_ptr(), (step.one if go_t is None else go_t).data_ptr()
+                bp.d_endpoints = rt.ptr(d_ep)
+                if ep_adam is not None:
+                    s0 = ep_adam.slot[0]
+                    bp.ep_adam.p, bp.ep_adam.m, bp.ep_adam.v, bp.ep_adam.coef = s0.p, s0.m, s0.v, s0.coef
+                    bp.beta1, bp.beta2, bp.eps = ep_adam.beta1, ep_adam.beta2, ep_adam.eps
+                _tail_group(ctx, step, pb.head_tail, scratch, out)
+                go, (g_means2D, _, _, _, g_sh, _, _) = _head_raster_backward(
+                    ctx, step, go_t, xyz, scale, quat, shs, planes, radii, geom, binning, img, scratch, out, endpoints, None, E,
+                    params=pb, plan=bp)
+                if plan is not None:
+                    plan.applied()
+                step.last["dmean2D"] = g_means2D
+                return (d_ep, d_w, d_o, d_m, *_split_sh(ctx, g_sh), None)
             go, (g_means2D, _, _, _, g_sh, _, _) = _head_raster_backward(
                 ctx, step, go, xyz, scale, quat, shs, planes, radii, geom, binning, img, scratch, out, endpoints, None, E,
                 params=pb)
@@ -578,6 +673,10 @@ class FusedStrandStep:
         self.fuse_preprocess = bool(getattr(opt, "fuse_preprocess", True)) and os.environ.get("HGS_FUSE_PREPROCESS", "1") != "0"
         # the backward mirror: parameters' backward in the rasterizer backward's per-Gaussian lanes (hgs_backward_multi_params)
         self.fuse_param_backward = bool(getattr(opt, "fuse_param_backward", True)) and os.environ.get("HGS_FUSE_PARAM_BACKWARD", "1") != "0"
+        # the endpoint gather inside that launch, by workgroups that own whole strands (hgs_backward_multi_params_planned), where the
+        # topology has a block plan (refresh()); off: the gather stays a launch of its own
+        self.fuse_endpoint_gather = (bool(getattr(opt, "fuse_endpoint_gather", True))
+                                     and os.environ.get("HGS_FUSE_ENDPOINT_GATHER", "1") != "0")
         # Adam in the backward's own lanes (include/hgs.h HgsAdamSlot; enable_inline_adam): the model's FusedAdam or None
         self.inline_adam = None
         # True: the loss terms (loss(), terms()) are complete only once backward() has run -- the head's last sums ride in
@@ -651,7 +750,7 @@ class FusedStrandStep:
         E = g._endpoints.shape[0]
         cached = getattr(g, "_adjacency_cache", None)
         if cached is not None and cached[0] is g.endpoint_pairs and cached[1] is self.smooth_pairs and cached[2] == E:
-            self.ep_segments, self.ep_pairs = cached[3], cached[4]
+            self.ep_segments, self.ep_pairs, self.block_plan = cached[3], cached[4], cached[5]
             return
         self.ep_segments = _adjacency(g.endpoint_pairs.reshape(-1), 2, E, 2)
         self.ep_pairs = None
@@ -659,7 +758,12 @@ class FusedStrandStep:
             self.ep_pairs = _adjacency(self.smooth_pairs.reshape(-1), 4, E, 4)
             if self.ep_pairs is None:
                 self.ep_segments = None
-        g._adjacency_cache = (g.endpoint_pairs, self.smooth_pairs, E, self.ep_segments, self.ep_pairs)
+        # the block plan (include/hgs.h HgsBlockPlan): workgroups of the backward's per-Gaussian launch that own whole strands, so
+        # that the launch is also the endpoint gather; None (no such partition, or scatter mode): the two launches stay
+        self.block_plan = None
+        if self.ep_segments is not None:
+            self.block_plan = _block_plan(self.ep_segments, g.endpoint_pairs.shape[0])
+        g._adjacency_cache = (g.endpoint_pairs, self.smooth_pairs, E, self.ep_segments, self.ep_pairs, self.block_plan)
 
     def loss(self):
         """(total loss, terms tensor) of the CURRENT slot view; differentiable w.r.t. the model parameters."""

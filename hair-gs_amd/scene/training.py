@@ -427,6 +427,8 @@ class GraphedStep:
     def _make_capturable(self):
         opt_ = self.g.optimizer
         dev = self.g.get_xyz.device
+        if hasattr(opt_, "ticket_words"):
+            opt_.ticket_words(dev)      # (FusedAdam: like the state below, not inside the capture)
         for group in opt_.param_groups:
             if isinstance(opt_, torch.optim.Adam):
                 group["capturable"] = True

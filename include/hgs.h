@@ -428,6 +428,48 @@ int hgs_backward_multi_params(void* stream, int P, int D, int M, int R, int W, i
                               const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
                               float tan_fovy, const int* radii, const void* geom_buf, const void* binning_buf, const void* image_buf,
                               const float* const* dL_dpix_planes7, void* scratch, float* dL_dsh, const HgsParamBackward* params);
+/* ---- hgs_backward_multi_params_planned (HGS_PARAMS_HAIR): hgs_backward_multi_params AND hgs_hair_endpoint_gather as ONE launch.
+ *   The gather is a launch of its own only because an endpoint's two segments may sit in different workgroups of the per-Gaussian
+ *   launch.  A BLOCK PLAN cuts the segments into chunks that own whole strands: workgroup c takes the segments
+ *   [s0, s0 + ns) (storage order, 1 <= ns <= 256) and the ne <= 256 endpoints ep_list[e0 .. e0 + ne); every segment and every
+ *   endpoint belongs to exactly one chunk, and every segment an endpoint's ep_segments codes name lies in that endpoint's chunk.
+ *   The segments' contributions then meet in LDS: behind one workgroup barrier lane t sums endpoint ep_list[e0 + t] exactly as
+ *   hgs_hair_endpoint_gather does (segment codes 0, 1, then pair roles 0..3), stores d_endpoints and applies the endpoint's Adam
+ *   update (ep_adam.p != NULL).  No workgroup waits for another one; seg_contrib is neither written nor read (it may be NULL).
+ *   The barrier also orders the lanes' reads of the endpoints in front of that update, and nothing behind it reads an endpoint:
+ *   the pairs' gradients arrive precomputed, i.e. a smoothness term (n_smooth > 0 with ep_pairs) REQUIRES smooth_pair_grads.
+ *   A deferred loss-head tail (params->head_tail.out != NULL) rides in one spare workgroup behind the chunks.
+ *   Results against the two launches: the endpoint sums, the parameter arithmetic and the Adam updates are the same operations in
+ *   the same order, so the results are the two launches' BIT FOR BIT wherever the per-Gaussian row sums are -- with
+ *   HGS_ROWS_REDUCE (row_reduce_kernel knows no wavefronts of Gaussians), and with the rows summed in the launch as long as no
+ *   wavefront streams its rows (no Gaussian with more than 32 instances: fresh strands).  The plan changes which 64 segments
+ *   form a wavefront, and with it which wavefronts stream and where a Gaussian's rows fall in the streamed run: on such a pass
+ *   the row sums of those wavefronts hold the same terms associated differently (as HGS_TILE_CULL above), the two forms agree
+ *   to that rounding -- every gradient of those Gaussians, their endpoints' and the Adam state behind them --, and each form
+ *   remains a fixed sequence of additions for a given pass (bitwise reproducible).  chunks / ep_list are DEVICE tables whose contents the host cannot see:
+ *   the kernel clamps what it reads from them to the model's sizes, but a table that breaks the rules above gives wrong
+ *   gradients.  plan == NULL: hgs_backward_multi_params.  A plan whose sizes, pointers or alignment are wrong is an error. ---- */
+typedef struct HgsBlockPlan {
+  int n_chunks;                         /* > 0 */
+  const int* chunks;                    /* [n_chunks][4] = s0, ns, e0, ne; 16-byte aligned */
+  const int* ep_list;                   /* [n_endpoints]: the chunks' endpoint ids, chunk after chunk */
+  int n_segments, n_endpoints;          /* what the chunks cover: n_segments must be the call's P */
+  const int* ep_segments;               /* [n_endpoints][2] as HgsStrandFusion.ep_segments; 8-byte aligned */
+  const int* ep_pairs;                  /* [n_endpoints][4] as HgsStrandFusion.ep_pairs, or NULL; 16-byte aligned */
+  const float* smooth_pair_grads;       /* [n_smooth][2][4] as HgsStrandFusion.smooth_pair_grads; 16-byte aligned */
+  int n_smooth;                         /* 0: no smoothness term */
+  const float* head_out; const float* grad_out;   /* the smoothness scale's inputs, as HgsStrandFusion (n_smooth > 0) */
+  float* d_endpoints;                   /* out [n_endpoints][3] */
+  HgsAdamSlot ep_adam;                  /* p != NULL: the endpoint lanes apply the update, with the betas / eps below */
+  float beta1, beta2, eps;
+} HgsBlockPlan;
+size_t hgs_block_plan_bytes(void);   /* sizeof(HgsBlockPlan) */
+int hgs_backward_multi_params_planned(void* stream, int P, int D, int M, int R, int W, int H, int flags, const float* bg7,
+                                      const float* means3D, const float* shs, const float* scales, const float* rotations,
+                                      const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                                      float tan_fovy, const int* radii, const void* geom_buf, const void* binning_buf,
+                                      const void* image_buf, const float* const* dL_dpix_planes7, void* scratch, float* dL_dsh,
+                                      const HgsParamBackward* params, const HgsBlockPlan* plan);
 /* d_endpoints [E,3] fully written.  fusion: ep_segments (required), ep_pairs + the smoothness group (smooth_pairs, n_smooth,
  * cos_threshold, eps, head_out, grad_out) and head_tail as for hgs_hair_params_backward; its other groups are ignored. */
 /* adam (may be NULL): slot 0 = the endpoints' Adam state; the lane then also applies endpoint i's update (HgsAdamSlot).  With a
