@@ -188,10 +188,15 @@ def _scene(name):
     if name == "strands_precomp":
         return strand_scene(n_strands=40, n_seg=50, W=200, H=120, seed=4, use_colors_precomp=True,
                             bg=(0.3, 0.3, 0.3))
+    if name == "hard_gaussians":
+        # Gaussians by class for the per-Gaussian backward (tests/gaussian_cases.py): clamped off-screen means, the near
+        # plane, needles end-on / on the diagonal, unnormalised quaternions, clamped SH channels; sh_degree 3, M = 16
+        from tests import gaussian_cases
+        return gaussian_cases.hard_scene("sh3")
     return random_scene(**VARIANTS[name])
 
 
-ALL = list(VARIANTS) + ["strands", "strands_precomp"]
+ALL = list(VARIANTS) + ["strands", "strands_precomp", "hard_gaussians"]
 
 
 def c1_cloud(device="cpu", n_strands=50, n_seg=20, seed=3):

@@ -51,8 +51,12 @@ def _assert_same_image(a, b, ranges):
 
 
 def _check_forward(name):
+    return _check_forward_scene(_scene(name))
+
+
+def _check_forward_scene(s):
+    """_check_forward on a scene dict (tests/test_gaussians_f64_gpu.py runs it on every input form of `hard_gaussians`)."""
     from tests import gpu_util as G
-    s = _scene(name)
     ref = O.forward(s)
     # the reference's own entry point with its 19 arguments (no culling): the tile lists are the reference's, every binning
     # stage is compared bit for bit.  render() and the training step cull instances that no pixel blends;

@@ -1227,22 +1227,48 @@ def test_one_launch_parameters_and_preprocess_equals_two_launches():
         assert torch.equal(a, b)
 
 
-def test_one_launch_cloud_parameters_and_preprocess_equals_two_launches():
+def _plant_hard_gaussians(model, cam):
+    """Overwrite the first rows of a cloud model's raw _xyz, _scaling (log) and _rotation with the classes of
+    tests/gaussian_cases.py, placed in the view space of `cam`: off-screen means beyond the 1.3 tan clamp, the near plane and
+    its cut, needles end-on and on the diagonal, scales of 1e-7, unnormalised quaternions.  The per-Gaussian backward is held
+    to float64 on them in tests/test_gaussians_f64_gpu.py; bit equality of the fused forms on the same rows carries that bar
+    to the launches training runs."""
+    import math
+    from tests import gaussian_cases
+    xyz, scales, quats = gaussian_cases.rows_in_camera(cam.world_view_transform.detach().cpu().numpy(), math.tan(cam.FoVx * 0.5),
+                                                       math.tan(cam.FoVy * 0.5))
+    n = xyz.shape[0]
+    assert n < model._xyz.shape[0]
+    dev = model._xyz.device
+    with torch.no_grad():
+        model._xyz[:n] = torch.from_numpy(xyz).to(dev)
+        model._scaling[:n] = torch.log(torch.from_numpy(scales).to(dev))
+        model._rotation[:n] = torch.from_numpy(quats).to(dev)
+
+
+@pytest.mark.parametrize("rows", ["cloud", "hard_gaussians"])
+def test_one_launch_cloud_parameters_and_preprocess_equals_two_launches(rows):
     """hgs_params_forward_preprocess against hgs_params_forward + hgs_forward_preprocess (Stage-I cloud iteration): loss
-    terms, image, radii and every parameter gradient bit for bit."""
+    terms, image, radii and every parameter gradient bit for bit; `hard_gaussians`: with the classes of tests/gaussian_cases.py
+    planted in camera 0's view space (_plant_hard_gaussians)."""
     from arguments import OptimizationParams
     from diff_gaussian_rasterization import _C as raster
     from hgs_runtime.strand_step import FusedCloudStep, ViewTable
     from synthetic import attach_targets, cameras_extent, make_cameras, make_cloud_model
     cams = make_cameras(4, 200, 120, device="cuda")
     model = make_cloud_model(3000, device="cuda", spatial_lr_scale=cameras_extent(cams))
+    if rows == "hard_gaussians":
+        _plant_hard_gaussians(model, cams[0])
     attach_targets(cams, model)
     opt = OptimizationParams()
     model.training_setup(opt)
     params = [model._xyz, model._scaling, model._rotation, model._opacity, model._mask, model._features_dc]
     out = {}
     try:
-        raster.set_async(True, slack=2.0)
+        # (the capacity is learnt from view 0, where culling drops most instances of the planted rows -- ~4000 stay; from the
+        # other views they need up to 5 times as many, and 2 x would void the pass with HgsCapacityOverflow.  8 x + 4096 >= 32.7 k
+        # holds every view: the planted rows' rectangles without any culling are <= 23.2 k instances in each of the four)
+        raster.set_async(True, slack=2.0 if rows == "cloud" else 8.0)
         for fuse in (False, True):
             views = ViewTable(cams)
             step = FusedCloudStep(model, views, opt, torch.zeros(3, device="cuda"))
@@ -1312,15 +1338,19 @@ def test_fused_parameter_backward_equals_two_launches():
             assert bool(a[3].abs().sum() > 0) and bool(a[-1].sum() > 0)
 
 
-def test_fused_cloud_parameter_backward_equals_two_launches():
+@pytest.mark.parametrize("rows", ["cloud", "hard_gaussians"])
+def test_fused_cloud_parameter_backward_equals_two_launches(rows):
     """hgs_backward_multi_params(HGS_PARAMS_CLOUD) against hgs_backward + hgs_cloud_params_backward (Stage-I cloud): the
     launch of the parameters' backward is gone, its results -- gradients of all seven parameter groups, statistics, loss terms
-    (the deferred tail rides in the rasterizer backward's spare workgroup) -- bit for bit."""
+    (the deferred tail rides in the rasterizer backward's spare workgroup) -- bit for bit; `hard_gaussians`: with the classes of
+    tests/gaussian_cases.py planted in camera 0's view space (_plant_hard_gaussians)."""
     from arguments import OptimizationParams
     from hgs_runtime.strand_step import FusedCloudStep, ViewTable
     from synthetic import attach_targets, cameras_extent, make_cameras, make_cloud_model
     cams = make_cameras(4, 200, 120, device="cuda")
     model = make_cloud_model(3000, device="cuda", spatial_lr_scale=cameras_extent(cams))
+    if rows == "hard_gaussians":
+        _plant_hard_gaussians(model, cams[0])
     attach_targets(cams, model)
     opt = OptimizationParams()
     model.training_setup(opt)
