@@ -3,7 +3,7 @@
 merge.py that the reference leaves to scripts/convert_output.py (MeshLab PLYs of the joints only).
   python export_strands.py -m <model dir | strand PLY> [-s <capture>] -o <out> --format hair|usc|ply_edges|ply_faces|npz [--format ...]
                            [--points 100] [--min_segments 1] [--min_length 0] [--max_root_distance D] [--colour model|strand]
-                           [--device cuda|cpu]
+                           [--device cuda|cpu] [--interpolate [--roots N] [--guides 4] [--max_guide_distance D] [--max_angle 60] [--no_guides]]
 A model directory is read at its newest point_cloud/iteration_N (utils/system.py model_ply, as eval.py reads it); the SH degree is read off the file.  Every
 strand is resampled by arc length to --points points (0: its joints as they are) with per-point colour, opacity and width
 (scene/strand_export.py: the contract; --device cuda = the HIP kernels on the model's device tensors, cpu = the numpy path), strands
@@ -15,7 +15,13 @@ strand root are dropped, and one file per --format is written (data/strand_files
   ply_faces  <out>.ply    one thin triangle per segment, for viewers without polylines (<out>_faces.ply if ply_edges is also asked for)
   npz        <out>.npz    the keys of hair_eval_data.npz (oriented points)
 The strand roots come from the model file; -s names a capture whose head_reconstruction_data.npz replaces them (needed only where
-the file has none).  --colour strand gives the PLYs one hue per strand instead of the model's colours."""
+the file has none).  --colour strand gives the PLYs one hue per strand instead of the model's colours.
+--interpolate turns the exported strands into guides of a dense groom (scene/groom.py: the contract): every strand root -- the file's,
+or with -s the capture's scalp points, --roots N of them taken evenly -- gets a strand blended from its --guides nearest guides by
+inverse squared distance; roots farther than --max_guide_distance from every guide's root get none, and guides whose root-to-tip
+direction turns more than --max_angle degrees from the nearest guide's are left out (a root at a parting follows one side).  The guides
+are written first (--no_guides: not at all), then the interpolated strands.  --points 0 has no fixed number of points to blend and is
+refused.  With -s and a head_sdf.npz in the capture, the number of interpolated points inside the head is printed."""
 import os
 import sys
 
@@ -68,6 +74,33 @@ def output_paths(out, formats):
     return {f: paths[f] for f in formats}
 
 
+def interpolated(args, model, guides):
+    """--interpolate: the exported strands as guides, a strand for every strand root blended from them (scene/groom.py), and the two
+    together (or, with --no_guides, the interpolated ones alone)."""
+    from scene.groom import concatenate, interpolate_strands
+    from utils.carve import select
+    roots = np.asarray(model.ref_strand_root, np.float64).reshape(-1, 3)
+    if args.roots is not None:
+        if args.roots < 0:
+            raise ValueError(f"--roots {args.roots}: a number of roots")
+        roots = roots[select(roots.shape[0], args.roots)]
+    groom = interpolate_strands(guides, roots, k=args.guides, max_guide_distance=args.max_guide_distance, max_angle=args.max_angle,
+                                device=None if args.device == "cpu" else args.device, first_id=model.strands_info.n_strands)
+    new = groom.strands
+    mean = float(groom.n_guides.mean()) if new.n_strands else 0.0
+    print(f"Interpolated: {roots.shape[0]} roots, {groom.n_dropped} dropped (no guide in reach), {new.n_strands} strands from "
+          f"{guides.n_strands} guides, {mean:.2f} guides per root on average")
+    if args.source_path is not None:
+        from utils import head_sdf
+        path = head_sdf.scene_sdf_path(args.source_path)
+        if os.path.exists(path):
+            _, _, d, in_range = head_sdf.sample(new.points, head_sdf.load_sdf(path))
+            with np.errstate(invalid="ignore"):
+                inside = int(np.count_nonzero(in_range & (d < 0)))
+            print(f"Inside the head ({path}): {inside} of {new.points.shape[0]} interpolated points (they are written as they are)")
+    return new if args.no_guides else concatenate(guides, new)
+
+
 def main(argv=None):
     parser = ArgumentParser(description="Export the strands of a trained model as hair assets")
     parser.add_argument("--model_path", "-m", required=True, help="a strand model PLY, or a model directory")
@@ -80,7 +113,16 @@ def main(argv=None):
     parser.add_argument("--max_root_distance", type=float, default=None)
     parser.add_argument("--colour", default="model", choices=["model", "strand"], help="vertex colours of the PLY outputs")
     parser.add_argument("--device", default="cuda", choices=["cuda", "cpu"], help="cuda: the HIP kernels; cpu: the numpy path")
+    parser.add_argument("--interpolate", action="store_true", help="add a strand for every strand root, blended from the nearest exported strands")
+    parser.add_argument("--roots", type=int, default=None, help="with --interpolate: take this many of the strand roots, evenly")
+    parser.add_argument("--guides", type=int, default=4, help="with --interpolate: guides blended per root (1 to 8)")
+    parser.add_argument("--max_guide_distance", type=float, default=None, help="with --interpolate: roots farther than this from every guide's root get no strand")
+    parser.add_argument("--max_angle", type=float, default=60.0, help="with --interpolate: guides whose chord turns more than this many degrees from the nearest guide's are left out")
+    parser.add_argument("--no_guides", action="store_true", help="with --interpolate: write the interpolated strands only")
     args = parser.parse_args(argv)
+    if args.interpolate and args.points == 0:
+        parser.exit(2, "export_strands.py: --interpolate blends strands point by point and needs a fixed number of points per strand: "
+                       "--points 0 (the joints themselves) cannot be combined with it\n")
     formats = list(dict.fromkeys(args.format or ["hair"]))
     from data import strand_files as F
     from scene.strand_export import resample_strands
@@ -92,6 +134,8 @@ def main(argv=None):
                               max_root_distance=args.max_root_distance, device=None if args.device == "cpu" else args.device)
     print(f"Strands: {model.strands_info.n_strands}, kept: {result.n_strands}, points: {result.points.shape[0]}"
           + (f" ({args.points} per strand)" if args.points else " (the joints)"))
+    if args.interpolate:
+        result = interpolated(args, model, result)
     paths = output_paths(args.output, formats)
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     for f in formats:

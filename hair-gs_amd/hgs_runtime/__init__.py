@@ -92,6 +92,8 @@ SIGNATURES = {
                                   vp, vp]),
     "hgs_strand_arclen": (ci, [vp, ci, vp, vp, C.c_longlong, vp, ci, vp, vp, vp]),
     "hgs_strand_resample": (ci, [vp, ci, vp, vp, vp, C.c_longlong, vp, ci, vp, ci, ci, vp, ci, vp, ci, vp, C.c_longlong, vp, vp]),
+    "hgs_groom_neighbours": (ci, [vp, ci, vp, ci, ci, vp, ci, C.c_double, C.c_double, vp, vp, vp, vp]),
+    "hgs_groom_blend": (ci, [vp, ci, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]),
     "hgs_undistort_images": (ci, [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci]),
     "hgs_rescale_images": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp, ci]),
     "hgs_rescale_orientation": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),

@@ -686,6 +686,28 @@ int hgs_strand_resample(void* stream, int S, const long long* offsets, const lon
                         const float* endpoints, int n_ep, const float* attr, int P, int C, const double* cum, int K, const int* kept,
                         int M, const long long* out_offsets, long long n_out, float* out_points, float* out_attrs);
 
+/* hgs_groom_neighbours / hgs_groom_blend (csrc/hgs_groom.hip) <-> the groom interpolation (scene/groom.py, export_strands.py --interpolate;
+ *   the reference has nothing of the kind): a strand for every root, blended from its nearest guides.  Guides: guide_points [K][M][3] and
+ *   guide_attrs [K][M][C], float32, M >= 2, 1 <= C <= 16; roots [N][3], float64.  All arithmetic float64 on these inputs, operation by
+ *   operation, results rounded once to float32 (scene/groom.py states the contract in full).
+ *   _neighbours, one lane per root: among the guides g (ascending) whose d2 = (dx*dx + dy*dy) + dz*dz from the root to guide_points[g][0]
+ *   is finite and <= max_d2 (+inf: no limit), the k (1..8) smallest by (d2, g).  Rank 0 is kept; rank i >= 1 is kept iff the chords
+ *   c = guide_points[g][M-1] - guide_points[g][0] of both have a length sqrt((cx*cx + cy*cy) + cz*cz) > 0 and (cix*c0x + ciy*c0y) + ciz*c0z
+ *   >= cos_max * (len_i * len_0); if d2 of rank 0 is 0 only rank 0 is kept.  w_i = d2_0 / d2_i (w_0 = 1), W = their sum in rank order
+ *   from 0.0.  Written, compacted in rank order: idx [N][k] int32, d2 [N][k] and w [N][k] = w_i / W float64, count [N] int32; slots at or
+ *   past count hold -1, +inf and 0.  K == 0 is legal: every count is 0.
+ *   _blend, one lane per output point, for the n_kept roots kept[n_kept] (int32, ascending, every one in [0, N): the caller's duty,
+ *   N is not passed): point j of root n = kept[n'] goes to row n' M + j: coordinate c = (float)(roots[n][c] + acc), acc = 0.0 then
+ *   acc = acc + w[n][i] * ((double)guide_points[g_i][j][c] - (double)guide_points[g_i][0][c]) over the row's slots i in order up to the
+ *   first idx outside [0, K); attribute a = (float)acc of acc = acc + w[n][i] * (double)guide_attrs[g_i][j][a].  out_points
+ *   [n_kept M][3], out_attrs [n_kept M][C], float32; n_kept M is at most 2^31 - 1.  No atomics: bitwise reproducible.
+ *   Bad sizes (k, M, C out of range, negative counts, a NaN max_d2 or cos_max, kept roots without a guide) and null arguments return 1
+ *   before anything is launched; N == 0 and n_kept == 0 return 0. */
+int hgs_groom_neighbours(void* stream, int N, const double* roots, int K, int M, const float* guide_points, int k, double max_d2,
+                         double cos_max, int* idx, double* d2, double* w, int* count);
+int hgs_groom_blend(void* stream, int K, int M, int C, const float* guide_points, const float* guide_attrs, const double* roots, int k,
+                    const int* idx, const double* w, int n_kept, const int* kept, float* out_points, float* out_attrs);
+
 /* hgs_undistort_images (csrc/hgs_undistort.hip) <-> the undistortion of a COLMAP capture (utils/undistort.py, undistort.py; the reference
  *   leaves it to COLMAP's image_undistorter): N images [N][Hs][Ws][C] uint8 (C = 1, 3 or 4, PIL's layout) seen through the camera
  *   `model` (COLMAP's model id: SIMPLE_PINHOLE 0, PINHOLE 1, SIMPLE_RADIAL 2, RADIAL 3, OPENCV 4, FULL_OPENCV 6; any other is an error)
