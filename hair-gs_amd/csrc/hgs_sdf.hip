@@ -15,6 +15,7 @@
 //   out[0] = float(sum / E), 0 for E = 0.  Bitwise reproducible.
 // head_penalty_bwd_kernel: d_points = g * (upstream / E), upstream read from device memory: no host synchronisation anywhere.
 #include "hgs_common.h"
+#include "hgs_sdf_sample.h"
 
 #include <math.h>
 
@@ -102,8 +103,6 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-__device__ __forceinline__ float lerp1(float a, float b, float f) { return a + f * (b - a); }
-
 __global__ __launch_bounds__(SDF_BLOCK) void head_penalty_kernel(int E, const float* __restrict__ points, const float* __restrict__ phi,
                                                                  int nx, int ny, int nz, float ox, float oy, float oz, float inv_h,
                                                                  float margin, float* __restrict__ g, float* __restrict__ pen_out,
@@ -113,26 +112,17 @@ __global__ __launch_bounds__(SDF_BLOCK) void head_penalty_kernel(int E, const fl
   double mine = 0.0;
   if (e < E) {
     const float x = points[3 * (size_t)e], y = points[3 * (size_t)e + 1], z = points[3 * (size_t)e + 2];
-    const float tx = (x - ox) * inv_h, ty = (y - oy) * inv_h, tz = (z - oz) * inv_h;
-    // (finite and 0 <= t < n - 1: a NaN fails every comparison, +inf the second)
-    const bool in = tx >= 0.f && tx < (float)(nx - 1) && ty >= 0.f && ty < (float)(ny - 1) && tz >= 0.f && tz < (float)(nz - 1);
+    // (the sampling statement: hgs_sdf_sample.h, shared with hgs_collide.hip)
+    float tx, ty, tz;
+    const bool in = sdf_grid_coords(x, y, z, ox, oy, oz, inv_h, nx, ny, nz, tx, ty, tz);
     float pen = 0.f, gx = 0.f, gy = 0.f, gz = 0.f, d = INFINITY;
     if (in) {
-      const float flx = floorf(tx), fly = floorf(ty), flz = floorf(tz);
-      const int ix = (int)flx, iy = (int)fly, iz = (int)flz;               // 0 <= i <= n - 2
-      const float fx = tx - flx, fy = ty - fly, fz = tz - flz;
-      const float* c = phi + ((size_t)iz * ny + iy) * nx + ix;
-      const size_t sy = (size_t)nx, szz = (size_t)nx * ny;
-      const float c000 = c[0], c100 = c[1], c010 = c[sy], c110 = c[sy + 1];
-      const float c001 = c[szz], c101 = c[szz + 1], c011 = c[szz + sy], c111 = c[szz + sy + 1];
-      const float c00 = lerp1(c000, c100, fx), c10 = lerp1(c010, c110, fx), c01 = lerp1(c001, c101, fx), c11 = lerp1(c011, c111, fx);
-      const float c0 = lerp1(c00, c10, fy), c1 = lerp1(c01, c11, fy);
-      d = lerp1(c0, c1, fz);
+      const SdfCell cell = sdf_cell(phi, nx, ny, tx, ty, tz);
+      d = sdf_value(cell);
       const float r = margin - d;
       if (r > 0.f) {
-        const float dx = lerp1(lerp1(c100 - c000, c110 - c010, fy), lerp1(c101 - c001, c111 - c011, fy), fz) * inv_h;
-        const float dy = lerp1(lerp1(c010 - c000, c110 - c100, fx), lerp1(c011 - c001, c111 - c101, fx), fz) * inv_h;
-        const float dz = lerp1(lerp1(c001 - c000, c101 - c100, fx), lerp1(c011 - c010, c111 - c110, fx), fy) * inv_h;
+        float dx, dy, dz;
+        sdf_gradient(cell, inv_h, dx, dy, dz);
         const float s = -2.f * r;
         pen = r * r;
         gx = s * dx; gy = s * dy; gz = s * dz;

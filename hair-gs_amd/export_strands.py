@@ -4,6 +4,7 @@ merge.py that the reference leaves to scripts/convert_output.py (MeshLab PLYs of
   python export_strands.py -m <model dir | strand PLY> [-s <capture>] -o <out> --format hair|usc|ply_edges|ply_faces|npz [--format ...]
                            [--points 100] [--min_segments 1] [--min_length 0] [--max_root_distance D] [--colour model|strand]
                            [--device cuda|cpu] [--interpolate [--roots N] [--guides 4] [--max_guide_distance D] [--max_angle 60] [--no_guides]]
+                           [--resolve_head [--head_margin 0] [--collide_iters 8] [--head_sdf PATH]]
 A model directory is read at its newest point_cloud/iteration_N (utils/system.py model_ply, as eval.py reads it); the SH degree is read off the file.  Every
 strand is resampled by arc length to --points points (0: its joints as they are) with per-point colour, opacity and width
 (scene/strand_export.py: the contract; --device cuda = the HIP kernels on the model's device tensors, cpu = the numpy path), strands
@@ -21,7 +22,13 @@ or with -s the capture's scalp points, --roots N of them taken evenly -- gets a 
 inverse squared distance; roots farther than --max_guide_distance from every guide's root get none, and guides whose root-to-tip
 direction turns more than --max_angle degrees from the nearest guide's are left out (a root at a parting follows one side).  The guides
 are written first (--no_guides: not at all), then the interpolated strands.  --points 0 has no fixed number of points to blend and is
-refused.  With -s and a head_sdf.npz in the capture, the number of interpolated points inside the head is printed."""
+refused.  With -s and a head_sdf.npz in the capture, the number of interpolated points inside the head is printed.
+--resolve_head pushes every strand that will be written out of the head (scene/strand_collide.py: the contract): after the resampling
+and --interpolate, before the writers, a joint closer to the head than --head_margin (scene units, inside counting as negative) is
+moved out along the gradient of the capture's distance field -- --head_sdf, by default <-s>/head_sdf.npz, which head_sdf.py writes --
+in at most --collide_iters pushes (1 to 32), and the joints behind it keep their segments' lengths and return to their path.  Roots do
+not move and attributes are untouched; the points inside before and after, the points moved, those left inside and the largest
+displacement are printed.  It works on ragged strands (--points 0) too.  Without the flag the strands are written as they are."""
 import os
 import sys
 
@@ -93,12 +100,31 @@ def interpolated(args, model, guides):
     if args.source_path is not None:
         from utils import head_sdf
         path = head_sdf.scene_sdf_path(args.source_path)
-        if os.path.exists(path):
+        if os.path.exists(path) and not args.resolve_head:       # (--resolve_head reports, and removes, the points inside)
             _, _, d, in_range = head_sdf.sample(new.points, head_sdf.load_sdf(path))
             with np.errstate(invalid="ignore"):
                 inside = int(np.count_nonzero(in_range & (d < 0)))
             print(f"Inside the head ({path}): {inside} of {new.points.shape[0]} interpolated points (they are written as they are)")
     return new if args.no_guides else concatenate(guides, new)
+
+
+def head_field_path(args):
+    """--resolve_head: the distance field's file, --head_sdf or the capture's; None where there is none."""
+    from utils import head_sdf
+    path = args.head_sdf if args.head_sdf is not None else (head_sdf.scene_sdf_path(args.source_path) if args.source_path is not None else None)
+    return path if path is not None and os.path.exists(path) else None
+
+
+def resolved(args, path, strands):
+    """--resolve_head: the strands pushed out of the head of the field at `path` (scene/strand_collide.py), and what that did."""
+    from scene.strand_collide import resolve_head
+    from utils import head_sdf
+    out, st = resolve_head(strands, head_sdf.load_sdf(path), margin=args.head_margin, iters=args.collide_iters,
+                           device=None if args.device == "cpu" else args.device)
+    print(f"Resolved against the head ({path}, margin {args.head_margin:g}): inside the head before: {st['inside_before']} of {st['joints']} "
+          f"points, after: {st['inside_after']} (deepest {st['deepest_before']:.4g} -> {st['deepest_after']:.4g}); moved {st['moved']} points "
+          f"of {st['strands_touched']} strands, unresolved: {st['unresolved']}, largest displacement {st['largest_displacement']:.4g}")
+    return out
 
 
 def main(argv=None):
@@ -119,7 +145,23 @@ def main(argv=None):
     parser.add_argument("--max_guide_distance", type=float, default=None, help="with --interpolate: roots farther than this from every guide's root get no strand")
     parser.add_argument("--max_angle", type=float, default=60.0, help="with --interpolate: guides whose chord turns more than this many degrees from the nearest guide's are left out")
     parser.add_argument("--no_guides", action="store_true", help="with --interpolate: write the interpolated strands only")
+    parser.add_argument("--resolve_head", action="store_true", help="push every strand out of the head, keeping its segments' lengths")
+    parser.add_argument("--head_margin", type=float, default=0.0, help="with --resolve_head: keep the joints this far outside the head")
+    parser.add_argument("--collide_iters", type=int, default=8, help="with --resolve_head: pushes per joint at most (1 to 32)")
+    parser.add_argument("--head_sdf", default=None, help="with --resolve_head: the head's distance field; default: <source_path>/head_sdf.npz")
     args = parser.parse_args(argv)
+    field = None
+    if args.resolve_head:
+        if not (np.isfinite(args.head_margin) and args.head_margin >= 0.0):
+            parser.exit(2, f"export_strands.py: --head_margin {args.head_margin}: a finite distance >= 0\n")
+        if not 1 <= args.collide_iters <= 32:
+            parser.exit(2, f"export_strands.py: --collide_iters {args.collide_iters}: 1 to 32\n")
+        field = head_field_path(args)
+        if field is None:
+            parser.exit(2, "export_strands.py: --resolve_head needs the head's distance field and found none"
+                           + (f" at {args.head_sdf}" if args.head_sdf is not None else
+                              f" at {os.path.join(args.source_path, 'head_sdf.npz')}" if args.source_path is not None else " (no -s and no --head_sdf)")
+                           + ": run head_sdf.py on the capture, or name a field with --head_sdf\n")
     if args.interpolate and args.points == 0:
         parser.exit(2, "export_strands.py: --interpolate blends strands point by point and needs a fixed number of points per strand: "
                        "--points 0 (the joints themselves) cannot be combined with it\n")
@@ -136,6 +178,8 @@ def main(argv=None):
           + (f" ({args.points} per strand)" if args.points else " (the joints)"))
     if args.interpolate:
         result = interpolated(args, model, result)
+    if args.resolve_head:
+        result = resolved(args, field, result)
     paths = output_paths(args.output, formats)
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     for f in formats:

@@ -111,6 +111,7 @@ SIGNATURES = {
     "hgs_head_penalty_num_blocks": (ci, [ci]),
     "hgs_head_penalty_forward": (ci, [vp, ci, vp, vp, ci, ci, ci, cf, cf, cf, cf, cf, vp, vp, vp, vp, vp]),
     "hgs_head_penalty_backward": (ci, [vp, ci, vp, vp, vp]),
+    "hgs_strand_collide": (ci, [vp, ci, vp, C.c_longlong, vp, vp, ci, ci, ci, cf, cf, cf, cf, cf, cf, ci, vp, vp, vp]),
     "hgs_field_splat": (ci, [vp, ci, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, C.c_double, vp, vp]),
     "hgs_field_solve": (ci, [vp, ci, ci, ci, vp, vp, vp]),
     "hgs_strand_trace": (ci, [vp, ci, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, C.c_double, ci,

@@ -36,8 +36,9 @@ up in segment order (one numpy statement for both paths); the kept root numbers 
 number of guides behind every kept root.
 
 What this does not do: the guides' offsets are not rotated to the local scalp normal, there is no jitter or clumping, and no
-collision response -- an interpolated strand can pass through the head (export_strands.py counts such points where it has the
-capture's distance field; pushing them out is another step).
+collision response of its own -- an interpolated strand can pass through the head.  Pushing such points out is the step behind this
+one, scene/strand_collide.py (export_strands.py --resolve_head); without that flag export_strands.py counts them where it has the
+capture's distance field and writes them as they are.
 
 device=None: numpy, vectorised over the roots, with explicit loops over the at most 8 ranks so that the sums keep rank order.
 device="cuda": hgs_groom_neighbours / hgs_groom_blend on torch tensors, the kept list built by one nonzero between the launches.  The

@@ -301,11 +301,12 @@ def _lerp(u, v, f):
     return u + f * (v - u)
 
 
-def sample(points, sdf, margin=0.0):
-    """(pen f32 [E], g f32 [E, 3], d f32 [E], in_range bool [E]) of the contract's term; d = +inf out of range."""
+def trilinear(points, sdf):
+    """(in_range bool [E], d, gx, gy, gz f32 [E]) of the contract's term up to the interpolated distance and its gradient; rows out
+    of range hold the values of some valid cell (scene/strand_collide.py samples the field by this statement too)."""
     p = _points32(points)
     nx, ny, nz = sdf.shape
-    k, margin = sdf.inv_h32, np.float32(margin)
+    k = sdf.inv_h32
     with np.errstate(all="ignore"):
         t = (p - sdf.origin32[None, :]) * k
         top = np.array([nx - 1, ny - 1, nz - 1], np.float32)
@@ -324,6 +325,15 @@ def sample(points, sdf, margin=0.0):
         gx = _lerp(_lerp(c[1, 0, 0] - c[0, 0, 0], c[1, 1, 0] - c[0, 1, 0], fy), _lerp(c[1, 0, 1] - c[0, 0, 1], c[1, 1, 1] - c[0, 1, 1], fy), fz) * k
         gy = _lerp(_lerp(c[0, 1, 0] - c[0, 0, 0], c[1, 1, 0] - c[1, 0, 0], fx), _lerp(c[0, 1, 1] - c[0, 0, 1], c[1, 1, 1] - c[1, 0, 1], fx), fz) * k
         gz = _lerp(_lerp(c[0, 0, 1] - c[0, 0, 0], c[1, 0, 1] - c[1, 0, 0], fx), _lerp(c[0, 1, 1] - c[0, 1, 0], c[1, 1, 1] - c[1, 1, 0], fx), fy) * k
+    assert d.dtype == np.float32 and gx.dtype == np.float32 and gy.dtype == np.float32 and gz.dtype == np.float32
+    return ok, d, gx, gy, gz
+
+
+def sample(points, sdf, margin=0.0):
+    """(pen f32 [E], g f32 [E, 3], d f32 [E], in_range bool [E]) of the contract's term; d = +inf out of range."""
+    ok, d, gx, gy, gz = trilinear(points, sdf)
+    margin = np.float32(margin)
+    with np.errstate(all="ignore"):
         r = margin - d
         on = ok & (r > 0)
         pen = np.where(on, r * r, np.float32(0))

@@ -956,6 +956,28 @@ int hgs_head_penalty_forward(void* stream, int E, const float* points, const flo
                              float oz, float inv_h, float margin, float* g, float* pen, float* dist, double* partials, float* out);
 int hgs_head_penalty_backward(void* stream, int E, const float* g, const float* upstream, float* d_points);
 
+/* hgs_strand_collide (csrc/hgs_collide.hip) <-> the push-out of exported strands (scene/strand_collide.py states the contract and has
+ *   the numpy path; export_strands.py --resolve_head; the reference has nothing of the kind): every strand is walked from its root, a
+ *   joint inside the head (in range and d < margin) is pushed along the field's gradient to margin + skin, and every joint behind a
+ *   pushed one is put back at its segment's original length from its moved predecessor, aiming at its original place.
+ *   K strands, strand s owning points offsets[s] .. offsets[s + 1] - 1 of points [P][3] float32; offsets [K + 1] int64 with
+ *   offsets[0] == 0, non-decreasing, offsets[K] == P: the caller's duty (a strand whose range does not lie inside the P points is
+ *   skipped, its counts 0).  phi [nz][ny][nx] float32 with origin and 1/h rounded to float32, sampled by hgs_head_penalty_forward's
+ *   statement at float32(x) (csrc/hgs_sdf_sample.h: one definition for both).  Per strand with joints p_0 .. p_{n-1} (n < 2: copied),
+ *   float64, one rounding per operation, dot(u, v) = (u0*v0 + u1*v1) + u2*v2: q_0 = p_0; for j = 1 .. n-1: e = p_j - p_{j-1},
+ *   L = sqrt(dot(e, e)); relen(x) = q_{j-1} + (L / lu) * u for u = x - q_{j-1}, lu = sqrt(dot(u, u)), where L and lu are finite and
+ *   lu > 0, else q_{j-1} + e; x = p_j, or relen(p_j) once a joint of the strand has been pushed; then at most iters (1..32) times:
+ *   sample (d, g) at x, stop unless in range and d < margin, gn = sqrt(dot(g, g)), stop unless gn is finite and > 0,
+ *   x = relen(x + (((margin + skin) - d) / gn) * g).  out_points[j] = float32(x); a joint that was pushed at least once adds one to
+ *   moved[s]; a joint whose written place is in range with d < margin adds one to unresolved[s].  margin, skin: finite, >= 0.
+ *   out_points [P][3] float32 must not alias points; moved, unresolved [K] int32.  One lane per strand, no atomics: bitwise
+ *   reproducible.  Bad sizes (negative counts, iters out of range, a margin or skin that is negative or not finite, an axis < 2 or
+ *   > 1024, an origin or 1/h that is not finite) and, for K > 0, null or aliased pointers return 1 before anything is launched;
+ *   K == 0 returns 0. */
+int hgs_strand_collide(void* stream, int K, const long long* offsets, long long P, const float* points, const float* phi, int nx, int ny,
+                       int nz, float ox, float oy, float oz, float inv_h, float margin, float skin, int iters, float* out_points,
+                       int* moved, int* unresolved);
+
 /* Strands traced from the scalp through the lifted hair directions (csrc/hgs_trace.hip; utils/trace.py states the contract and has
  *   the numpy paths).  All float64, one rounding per operation.  Every argument is checked before a pointer is touched.  The grid:
  *   node (ix, iy, iz) lies at origin + index * h, 2 <= n <= 1024 an axis, at most 2^26 nodes in all.
