@@ -120,11 +120,12 @@ def forward(inp, f64=False, render=True):
     return o
 
 
-def backward(inp, fwd, dL_dpix, f64=False, pixel_mask=False):
+def backward(inp, fwd, dL_dpix, f64=False, pixel_mask=False, acc_abs=False):
     """Full backward given the forward's intermediates.  Output names/shapes follow
     DGR/rasterize_points.cu:151-159 (dL_dconic is [P,2,2] with element [1,0] unused).
     pixel_mask=True adds g["fragile_pixels"], an [H, W] bool array of the pixels that hold a near-threshold decision
-    (raster_oracle.c; it depends on the forward state only, not on dL_dpix)."""
+    (raster_oracle.c; it depends on the forward state only, not on dL_dpix).
+    acc_abs=True adds g["acc_abs"], [P, 9] float64: the sum of the magnitudes of the terms behind each element of g["acc"]."""
     dt, cr, sfx = _real(f64)
     L = lib()
     n = normalize_inputs(inp, f64)
@@ -135,11 +136,12 @@ def backward(inp, fwd, dL_dpix, f64=False, pixel_mask=False):
     fragile = np.zeros(P, np.uint8)   # Gaussians with a near-threshold (pixel, entry) decision (raster_oracle.c)
     touched = np.zeros(P, np.uint8)   # Gaussians blended at a pixel that holds such a decision (its transmittance chain moves)
     pmask = np.zeros(H * W, np.uint8) if pixel_mask else None
+    aabs = np.zeros((P, 9), np.float64) if acc_abs else None
     getattr(L, "hgs_oracle_render_backward" + sfx)(C.c_int(P), C.c_int(W), C.c_int(H), _p(fwd["ranges"]),
                                                    _p(fwd["point_list"]), _p(n["bg"]), _p(fwd["means2D"]),
                                                    _p(fwd["conic_opacity"]), _p(feats), _p(fwd["final_T"]),
                                                    _p(fwd["n_contrib"]), _p(dpix), _p(acc), _p(fragile), _p(touched),
-                                                   _p(pmask))
+                                                   _p(pmask), _p(aabs))
     g = {
         "dL_dmeans2D": np.zeros((P, 3), dt), "dL_dconic": np.zeros((P, 4), dt), "dL_dopacity": np.zeros((P, 1), dt),
         "dL_dcolors": np.zeros((P, 3), dt), "dL_dmeans3D": np.zeros((P, 3), dt), "dL_dcov3D": np.zeros((P, 6), dt),
@@ -159,6 +161,8 @@ def backward(inp, fwd, dL_dpix, f64=False, pixel_mask=False):
         cr(n["tanfovy"]), _p(n["campos"]), _p(g["dL_dmeans2D"]), _p(g["dL_dconic"]), _p(g["dL_dmeans3D"]),
         _p(g["dL_dcolors"]), _p(g["dL_dcov3D"]), _p(g["dL_dsh"]), _p(g["dL_dscales"]), _p(g["dL_drotations"]))
     g["acc"] = acc
+    if acc_abs:
+        g["acc_abs"] = aabs
     g["fragile"] = fragile.astype(bool)
     g["touched"] = touched.astype(bool) | g["fragile"]
     if pixel_mask:
@@ -180,7 +184,7 @@ def fragile_pixels(inp, fwd, f64=False):
                                                        _p(fwd["point_list"]), _p(n["bg"]), _p(fwd["means2D"]),
                                                        _p(fwd["conic_opacity"]), _p(feats), _p(fwd["final_T"]),
                                                        _p(fwd["n_contrib"]), _p(np.zeros((3, H, W), dt)), _p(acc), None, None,
-                                                       _p(pmask))
+                                                       _p(pmask), None)
     return pmask.astype(bool).reshape(H, W)
 
 

@@ -123,6 +123,12 @@ void SYM(hgs_oracle_mat3_sandwich)(const real* t, const real* v, real* out) { /*
   memcpy(out, r.m, sizeof(r.m));
 }
 
+/* The exponential the blend below evaluates, on n values: tests/blend_reference.py restates the blend in numpy, whose own
+ * float32 exp is not libm's bit for bit. */
+void SYM(hgs_oracle_exp)(int64_t n, const real* x, real* out) {
+  for (int64_t i = 0; i < n; i++) out[i] = R_EXP(x[i]);
+}
+
 /* CR/auxiliary.h:58-66 */
 static void transformPoint4x3(const real p[3], const real* M, real out[3]) {
   out[0] = M[0] * p[0] + M[4] * p[1] + M[8] * p[2] + M[12];
@@ -423,6 +429,8 @@ void SYM(hgs_oracle_render)(int W, int H, const uint32_t* ranges, const uint32_t
  * Accumulators are double: the oracle returns the exactly-ordered sum of the per-(pixel,entry)
  * terms; the GPU's fp32 summation order is free (reference: float atomics).
  * acc layout per Gaussian: [dmean2D.x, dmean2D.y, dconic.x, dconic.y, dconic.w, dopacity, dcolor0..2]
+ * acc_abs (checker aid, same layout): the sum of the MAGNITUDES of the same terms -- the scale an fp32 summation of a
+ * row's terms in any order rounds at (tests/blend_reference.py builds its floors from it).
  * ------------------------------------------------------------------------------------------ */
 void SYM(hgs_oracle_render_backward)(int P, int W, int H, const uint32_t* ranges, const uint32_t* point_list,
                                      const real* bg, const real* means2D, const real* conic_opacity, const real* colors,
@@ -430,9 +438,11 @@ void SYM(hgs_oracle_render_backward)(int P, int W, int H, const uint32_t* ranges
                                      double* acc /* [P][9], zeroed here */,
                                      uint8_t* fragile /* [P] or NULL: see below */,
                                      uint8_t* touched /* [P] or NULL: see below */,
-                                     uint8_t* pixel_mask /* [H*W] or NULL: 1 where the pixel holds such a decision */) {
+                                     uint8_t* pixel_mask /* [H*W] or NULL: 1 where the pixel holds such a decision */,
+                                     double* acc_abs /* [P][9] or NULL, zeroed here: sum of |term| per accumulator */) {
   const int gx = (W + BLOCK_X - 1) / BLOCK_X, gy = (H + BLOCK_Y - 1) / BLOCK_Y;
   memset(acc, 0, (size_t)P * 9 * sizeof(double));
+  if (acc_abs) memset(acc_abs, 0, (size_t)P * 9 * sizeof(double));
   const real ddelx_dx = (real)(0.5 * W), ddely_dy = (real)(0.5 * H);
   const int mark = fragile != NULL || pixel_mask != NULL; /* look for near-threshold decisions at all */
 #pragma omp parallel for schedule(dynamic, 1)
@@ -486,6 +496,10 @@ void SYM(hgs_oracle_render_backward)(int P, int W, int H, const uint32_t* ranges
             double v = (double)(dchannel_dcolor * dL_dchannel);
 #pragma omp atomic
             a[6 + ch] += v;
+            if (acc_abs) {
+#pragma omp atomic
+              acc_abs[9 * (size_t)id + 6 + ch] += fabs(v);
+            }
           }
           dL_dalpha *= T;
           last_alpha = alpha;
@@ -511,6 +525,13 @@ void SYM(hgs_oracle_render_backward)(int P, int W, int H, const uint32_t* ranges
           a[4] += v4;
 #pragma omp atomic
           a[5] += v5;
+          if (acc_abs) {
+            const double va[6] = {fabs(v0), fabs(v1), fabs(v2), fabs(v3), fabs(v4), fabs(v5)};
+            for (int q = 0; q < 6; q++) {
+#pragma omp atomic
+              acc_abs[9 * (size_t)id + q] += va[q];
+            }
+          }
         }
         /* Checker aid, second part: a decision that an implementation takes the other way changes this PIXEL's transmittance
          * chain by that entry's alpha (~1/255) and the colour behind every nearer entry -- i.e. the terms of EVERY Gaussian the
