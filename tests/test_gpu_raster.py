@@ -13,6 +13,7 @@ import pytest
 
 from oracle import hgs_oracle as O
 from tests import scenes
+from tests.binning_cases import SEG_POLICY, SPLIT_MIN_LEN   # (lists up to SPLIT_MIN_LEN entries are never split across workgroups)
 from tests.scenes import ALL, VARIANTS, _scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -26,9 +27,6 @@ def _forward(s, cull):
         return G.run_forward(s)
     finally:
         _C.set_tile_cull(was)
-
-
-SPLIT_MIN_LEN = 192   # csrc/hgs_blend.hip: tile lists up to this length are never split across workgroups
 
 
 def _long_tile_pixels(ranges, W, H):
@@ -105,38 +103,14 @@ def test_forward_matches_oracle(name):
 def test_blend_work_list_covers_every_tile_once(name):
     """The blend kernels' work list (sort_tiles_kernel): split lists as consecutive ascending segments that tile the list
     exactly, every other tile exactly once in tile_order with list lengths (capped at 511) non-increasing."""
-    import hgs_runtime as rt
+    from tests import binning_reference as BR
     from tests import gpu_util as G
     s = _scene(name)
     fw = G.run_forward(s)
     W, H = s["W"], s["H"]
     T = ((W + 15) // 16) * ((H + 15) // 16)
-    lay = rt.layout("image", W, H)
-    img = fw["img"].cpu().numpy()
-    st = img[lay["status"]:lay["status"] + 64].view(np.uint32)
-    n_split_items, seg_len, n_work = int(st[5]), int(st[6]), int(st[7])
-    assert st[8] == 0 and 128 <= seg_len <= 1024 and seg_len % 64 == 0
-    work_list = G.blend_work_list(s, fw)
-    order = work_list[n_split_items:n_work]
-    assert (order >> 24 == 0).all()
-    ranges = img[lay["ranges"]:lay["ranges"] + 8 * T].view(np.uint32).reshape(T, 2)
-    n = (ranges[:, 1] - ranges[:, 0]).astype(np.int64)
-    split_tiles = {}
-    if n_split_items:
-        work = work_list[:n_split_items]
-        assert (work != 0xFFFFFFFF).all()
-        for pos, item in enumerate(work.tolist()):
-            split_tiles.setdefault(item & 0xFFFFFF, []).append((pos, item >> 24))
-        for t, segs in split_tiles.items():
-            pos, idx = zip(*segs)
-            assert list(idx) == list(range(len(idx))) and list(pos) == list(range(pos[0], pos[0] + len(pos))), t
-            assert n[t] > seg_len + seg_len // 2 and len(idx) <= 63
-            step = seg_len if -(-n[t] // seg_len) <= 63 else ((-(-n[t] // 63) + 63) // 64) * 64
-            assert len(idx) == -(-n[t] // step), (t, n[t], len(idx), step)
-    assert sorted(order.tolist() + list(split_tiles)) == list(range(T))
-    assert all(n[t] <= seg_len + seg_len // 2 for t in order.tolist())
-    L = np.minimum(n, 511)[order]
-    assert (np.diff(L) <= 0).all()
+    got = G.intermediates(s, fw)
+    split_tiles = BR.check_work_list(got["status"], G.blend_work_list(s, fw), got["ranges"], T, SEG_POLICY)
     if name in ("dense_long_lists", "medium_lists", "one_huge_tile"):
         assert split_tiles
 
