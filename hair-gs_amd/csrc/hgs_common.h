@@ -454,4 +454,15 @@ __device__ __forceinline__ uint32_t hgs_wave_incl_scan(uint32_t v, int lane) {
   }
   return v;
 }
+// float64 sum over the wavefront by an xor butterfly: each step adds the two halves of a pair, so every lane ends with the same
+// bits.  The association is part of the bit contracts of its users (hgs_normals.hip, hgs_view_stats.hip, hgs_sdf.hip).
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = HGS_WAVE / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off, HGS_WAVE);
+  return v;
+}
+// (a . b) in float64, associated as the numpy paths do (hgs_trace.hip, hgs_sdf.hip; both built with -ffp-contract=off)
+__device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) {
+  return (ax * bx + ay * by) + az * bz;
+}
 #endif

@@ -1,6 +1,7 @@
 // hgs_keysort.h -- Morton bit spreading and the bitonic sort of unique 64-bit keys (code << 32 | index) that the grid searches
-// share: distCUDA2 (hgs_knn.hip), the point-cloud normals (hgs_normals.hip) and the magnet term (hgs_magnet.hip).  Included into each translation unit's own
-// anonymous namespace; the kernels are the ones hgs_knn.hip has always launched, in the same order.
+// share: the grid of Morton cells (hgs_cellgrid.h: distCUDA2 and the magnet term) and the point-cloud normals (hgs_normals.hip).
+// Included into each translation unit's own anonymous namespace; the kernels are the ones hgs_knn.hip has always launched, in
+// the same order.
 #pragma once
 #include "hgs_common.h"
 
@@ -67,36 +68,6 @@ void keysort_launch(hipStream_t st, uint64_t* keys, size_t Npad) {
       hipLaunchKernelGGL(bitonic_global_kernel, dim3((unsigned)((Npad / 2 + 255) / 256)), dim3(256), 0, st, keys, Npad / 2, (int)k, (int)j);
     hipLaunchKernelGGL(bitonic_lds_kernel, dim3(nchunks), dim3(1024), 0, st, keys, (int)k, (int)j, false);
   }
-}
-
-// ---- what the searches over a grid of Morton cells share (hgs_knn.hip: distCUDA2; hgs_magnet.hip: the magnet term) ----
-// coordinate -> cell coordinate of the Morton kernels, saturating (NaN and negatives -> 0)
-__device__ __forceinline__ uint32_t f2u_sat(float v) {
-  if (!(v > 0.f)) return 0u;
-  if (v >= 4294967040.f) return 0xFFFFFFFFu;
-  return (uint32_t)v;
-}
-
-// squared distance of a point to a box, exactly as distBoxPoint (simple_knn.cu:120-130)
-__device__ __forceinline__ float box_point_dist2(const float* bx, float x, float y, float z) {
-  float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-  if (x < bx[0] || x > bx[3]) d0 = fminf(fabsf(x - bx[0]), fabsf(x - bx[3]));
-  if (y < bx[1] || y > bx[4]) d1 = fminf(fabsf(y - bx[1]), fabsf(y - bx[4]));
-  if (z < bx[2] || z > bx[5]) d2 = fminf(fabsf(z - bx[2]), fabsf(z - bx[5]));
-  return d0 * d0 + d1 * d1 + d2 * d2;
-}
-
-// ---- the cell table: per cell of level L (code >> (30 - 3 L)) [first, end) in the sorted array and the points' bounding box.
-// Floats are kept as order-preserving integers so that min / max are integer atomics (exact, order-independent).
-__device__ __forceinline__ int fkey(float v) { const int b = __float_as_int(v); return b >= 0 ? b : b ^ 0x7FFFFFFF; }   // monotone: a < b <=> fkey(a) < fkey(b)
-__device__ __forceinline__ float funkey(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7FFFFFFF); }
-
-__global__ __launch_bounds__(256) void cells_clear_kernel(uint32_t n_cells, uint32_t* __restrict__ cells) {
-  const uint32_t c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= n_cells) return;
-  uint4* t = (uint4*)(cells + 8 * (size_t)c);
-  t[0] = make_uint4(0u, 0u, (uint32_t)0x7FFFFFFF, (uint32_t)0x7FFFFFFF);              // first, end, min x, min y
-  t[1] = make_uint4((uint32_t)0x7FFFFFFF, 0x80000000u, 0x80000000u, 0x80000000u);     // min z, max x, max y, max z
 }
 
 }  // namespace

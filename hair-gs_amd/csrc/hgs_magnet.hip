@@ -10,8 +10,8 @@
 //             distance = dx*dx + dy*dy + dz*dz in float32 without contraction (bit-equal to hgs_knn3 on the same points):
 //               tiles  one query per lane, candidates staged through LDS as float4 (one broadcast 16-byte read each); for small n
 //                      the candidate range is split over workgroups and the partial triples are merged in the same order
-//               grid   Morton keys -> keysort_launch -> cell table with exact boxes -> own cell, then the cells the third-best
-//                      radius reaches (the plan of hgs_knn.hip's distCUDA2; here positions are kept and break ties)
+//               grid   the grid of Morton cells of hgs_cellgrid.h, which distCUDA2 searches too (keys -> keysort_launch -> cell
+//                      table -> own cell, then the cells the third-best radius reaches); here positions are kept and break ties
 //             select (statements (c)-(e) of include/hgs.h, per-workgroup float64 partial sums) -> finalize (value, rows)
 //   backward  no float atomics: keys (selected position << 32 | own position) of the kept rows -> keysort_launch -> one lane per
 //             destination sums its contributors in ascending order -> one store per end.  Same bits from run to run and under
@@ -19,15 +19,13 @@
 //             a handful of ends at most, but nothing bounds it -- n coincident ends all select one of three positions, and
 //             that lane then takes O(n) steps (correct and deterministic, slow; a cooperative sum in a fixed tree would bound
 //             it and is not built).
-#include <float.h>
 #include <limits.h>
 
 #include "hgs_common.h"
-#include "hgs_keysort.h"
+#include "hgs_cellgrid.h"
 
 namespace {
 
-#define MAG_NONFINITE_CODE 0x7FFFFFFFu   // Morton "code" of an end with a non-finite coordinate: behind every 30-bit code, in no cell
 #ifndef HGS_MAGNET_GRID_MIN
 // automatic mode: the grid from this many ends on.  Measured on an MI355X: forward at 2 10^4 ends 0.36 ms
 // through the tiles and 0.41 ms through the grid, at 2 10^5 ends 16.9 against 1.00 ms; the tiles grow with n^2, the grid with
@@ -37,14 +35,12 @@ namespace {
 
 int g_magnet_search = -1;   // hgs_set_magnet_search
 
-struct MagTriple { float d[3]; int i[3]; };   // ascending by (distance, position); empty slots: (+inf, -1)
-
 struct MagScratch {
   int* counts;          // [0] valid ends, [1] rows of the mean, [2..7] order-preserving keys of the valid finite ends' bounding box
   int* blk_count;       // valid ends per workgroup of 256 ends
   float4* cpts;         // the compacted list: position -> coordinates
   int2* cmeta;          // position -> (index into `ends`, partner's global id)
-  MagTriple* part;      // [splits][n] partial triples (tiles), [n] triples (grid)
+  Best3* part;          // [splits][n] partial triples (tiles), [n] triples (grid)
   uint64_t* keys;       // Npad sort keys (forward: Morton code << 32 | position; backward: selected << 32 | own)
   float4* sorted;       // grid: the valid ends in Morton order (w = position)
   uint32_t* cells;      // grid: 8 words per cell
@@ -53,11 +49,6 @@ struct MagScratch {
   float* nbsum;         // backward: per position the sum of its contributors' gradients
 };
 
-static int mag_level(size_t n) {          // about 16 ends per cell of a uniform cloud (hgs_knn.hip knn_level)
-  int L = 1;
-  while (L < 7 && ((size_t)1 << (3 * (L + 1))) * 16 <= n) L++;
-  return L;
-}
 static int mag_splits(int n) {            // tiles: workgroups per block of queries, so that a few thousand ends still fill the chip
   const int qb = (n + 255) / 256;
   int S = 512 / (qb > 0 ? qb : 1);
@@ -76,7 +67,7 @@ size_t mag_carve(char* base, size_t n, MagScratch& s) {      // (every array is 
   hgs_carve(cur, s.part, (size_t)mag_splits((int)n) * n + 1);
   hgs_carve(cur, s.keys, Npad);
   hgs_carve(cur, s.sorted, n + 1);
-  hgs_carve(cur, s.cells, 8 * ((size_t)1 << (3 * mag_level(n))));
+  hgs_carve(cur, s.cells, 8 * ((size_t)1 << (3 * cellgrid_level(n))));
   hgs_carve(cur, s.blk_sum, nb + 1);
   hgs_carve(cur, s.blk_rows, nb + 1);
   hgs_carve(cur, s.nbsum, 3 * n + 1);
@@ -152,7 +143,7 @@ __global__ __launch_bounds__(256) void mag_compact_kernel(int n, int E, const fl
 }
 
 // insert by (distance, position): what a walk in ascending position order gets from `d < b2` alone (knn3_kernel)
-__device__ __forceinline__ void mag_insert(MagTriple& b, float d, int pos) {
+__device__ __forceinline__ void mag_insert(Best3& b, float d, int pos) {
   if (d < b.d[2] || (d == b.d[2] && pos < b.i[2])) {
     if (d < b.d[1] || (d == b.d[1] && pos < b.i[1])) {
       b.d[2] = b.d[1]; b.i[2] = b.i[1];
@@ -161,175 +152,55 @@ __device__ __forceinline__ void mag_insert(MagTriple& b, float d, int pos) {
     } else { b.d[2] = d; b.i[2] = pos; }
   }
 }
-__device__ __forceinline__ void mag_clear(MagTriple& b) {
-  b.d[0] = b.d[1] = b.d[2] = INFINITY;
-  b.i[0] = b.i[1] = b.i[2] = -1;
-}
-__device__ __forceinline__ float mag_dist2(const float4& a, const float4& q) {
-  const float dx = a.x - q.x, dy = a.y - q.y, dz = a.z - q.z;
-  return dx * dx + dy * dy + dz * dz;      // (this file is built with -ffp-contract=off)
-}
 
 // ---- tiles: blockIdx.x = 256 queries, blockIdx.y = its share [y * chunk, (y + 1) * chunk) of the candidates
 __global__ __launch_bounds__(256) void mag_tiles_kernel(int n, int chunk, const int* __restrict__ counts,
-                                                        const float4* __restrict__ cpts, MagTriple* __restrict__ part) {
+                                                        const float4* __restrict__ cpts, Best3* __restrict__ part) {
   __shared__ float4 sp[256];
   const int nv = min(counts[0], n);
   if ((int)blockIdx.x * 256 >= nv) return;
   const int a = blockIdx.x * 256 + threadIdx.x;
   const float4 me = a < nv ? cpts[a] : make_float4(0.f, 0.f, 0.f, 0.f);
   const int t_begin = min((int)blockIdx.y * chunk, nv), t_end = min(t_begin + chunk, nv);
-  float b0 = INFINITY, b1 = INFINITY, b2 = INFINITY;
-  int i0 = -1, i1 = -1, i2 = -1;
+  Best3 b;
+  best3_clear(b);
   for (int t0 = t_begin; t0 < t_end; t0 += 256) {
     const int j = t0 + threadIdx.x;
     __syncthreads();
     if (j < t_end) sp[threadIdx.x] = cpts[j];
     __syncthreads();
     const int nbc = min(256, t_end - t0);
-    for (int k = 0; k < nbc; k++) {
-      const float d = mag_dist2(me, sp[k]);       // one broadcast 16-byte LDS read per candidate
-      if (d < b2) {                               // (positions ascend along the walk: an equal distance never displaces)
-        if (d < b1) {
-          b2 = b1; i2 = i1;
-          if (d < b0) { b1 = b0; i1 = i0; b0 = d; i0 = t0 + k; }
-          else { b1 = d; i1 = t0 + k; }
-        } else { b2 = d; i2 = t0 + k; }
-      }
-    }
+    for (int k = 0; k < nbc; k++) best3_push(b, point_dist2(me, sp[k]), t0, k);   // one broadcast 16-byte LDS read per candidate
   }
-  if (a < nv) {
-    MagTriple t;
-    t.d[0] = b0; t.d[1] = b1; t.d[2] = b2; t.i[0] = i0; t.i[1] = i1; t.i[2] = i2;
-    part[(size_t)blockIdx.y * n + a] = t;
-  }
+  if (a < nv) part[(size_t)blockIdx.y * n + a] = b;
 }
 
-// ---- grid
-__device__ __forceinline__ void mag_load_box(const int* __restrict__ counts, float* smm) {
-  if (threadIdx.x < 6) smm[threadIdx.x] = funkey(counts[2 + threadIdx.x]);
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void mag_morton_kernel(int n, int Npad, const int* __restrict__ counts, const float4* __restrict__ cpts,
-                                                         uint64_t* __restrict__ keys) {
-  __shared__ float smm[6];
-  mag_load_box(counts, smm);
-  const int nv = min(counts[0], n);
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= Npad) return;
-  if (i >= nv) { keys[i] = ~0ull; return; }
-  const float4 p = cpts[i];
-  uint32_t code = MAG_NONFINITE_CODE;
-  if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-    const uint32_t cx = prep_morton(min(f2u_sat(((p.x - smm[0]) / (smm[3] - smm[0])) * 1023), 1023u));
-    const uint32_t cy = prep_morton(min(f2u_sat(((p.y - smm[1]) / (smm[4] - smm[1])) * 1023), 1023u));
-    const uint32_t cz = prep_morton(min(f2u_sat(((p.z - smm[2]) / (smm[5] - smm[2])) * 1023), 1023u));
-    code = cx | (cy << 1) | (cz << 2);
+// ---- grid (hgs_cellgrid.h)
+// the magnet as a source of the grid: min(counts[0], n) valid ends, counted on the device (the op is captured in a graph); their
+// bounding box in counts[2..7] as order-preserving keys; an end with a non-finite coordinate is in no cell
+struct MagSource {
+  const int* __restrict__ counts;
+  static constexpr bool kGuarded = true;
+  __device__ __forceinline__ int live(int n) const { return min(counts[0], n); }
+  __device__ __forceinline__ void load_box(float* box) const {
+    if (threadIdx.x < 6) box[threadIdx.x] = funkey(counts[2 + threadIdx.x]);
+    __syncthreads();
   }
-  keys[i] = ((uint64_t)code << 32) | (uint32_t)i;
-}
+};
 
-__global__ __launch_bounds__(256) void mag_gather_kernel(int n, const int* __restrict__ counts, const float4* __restrict__ cpts,
-                                                         const uint64_t* __restrict__ keys, float4* __restrict__ sorted) {
-  const int nv = min(counts[0], n);
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nv) return;
-  const uint32_t pos = (uint32_t)keys[i];
-  float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (pos < (uint32_t)nv) p = cpts[pos];
-  p.w = __uint_as_float(pos);
-  sorted[i] = p;
-}
-
-__global__ __launch_bounds__(256) void mag_cells_mark_kernel(int n, int shift, const int* __restrict__ counts,
-                                                             const uint64_t* __restrict__ keys, const float4* __restrict__ sorted,
-                                                             uint32_t* __restrict__ cells) {
-  const int nv = min(counts[0], n);
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nv) return;
-  const uint32_t code = (uint32_t)(keys[i] >> 32);
-  if (code >= 0x40000000u) return;                                  // non-finite: in no cell
-  const uint32_t c = code >> shift;
-  const bool first = i == 0 || ((uint32_t)(keys[i - 1] >> 32) >> shift) != c;
-  bool last = i == nv - 1;
-  if (!last) {
-    const uint32_t nc = (uint32_t)(keys[i + 1] >> 32);
-    last = nc >= 0x40000000u || (nc >> shift) != c;
-  }
-  uint32_t* t = cells + 8 * (size_t)c;
-  if (first) t[0] = (uint32_t)i;
-  if (last) t[1] = (uint32_t)i + 1u;
-  const float4 p = sorted[i];
-  atomicMin((int*)&t[2], fkey(p.x)); atomicMin((int*)&t[3], fkey(p.y)); atomicMin((int*)&t[4], fkey(p.z));
-  atomicMax((int*)&t[5], fkey(p.x)); atomicMax((int*)&t[6], fkey(p.y)); atomicMax((int*)&t[7], fkey(p.z));
-}
-
-// one lane per end of the sorted array; the triple does not depend on the traversal (mag_insert orders by (distance, position))
-__global__ __launch_bounds__(256) void mag_grid_kernel(int n, int L, const int* __restrict__ counts, const float4* __restrict__ sorted,
-                                                       const uint64_t* __restrict__ keys, const uint32_t* __restrict__ cells,
-                                                       MagTriple* __restrict__ part) {
-  __shared__ float smm[6];
-  mag_load_box(counts, smm);
-  const int nv = min(counts[0], n);
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= nv) return;
-  const float4 me = sorted[idx];
-  const uint32_t mypos = __float_as_uint(me.w);
-  if (mypos >= (uint32_t)nv) return;
-  MagTriple best;
-  mag_clear(best);
-  const uint32_t code = (uint32_t)(keys[idx] >> 32);
-  if (code >= 0x40000000u) { part[mypos] = best; return; }          // compares closer to nothing: (+inf, -1) slots, as in the tiles
-  {
-    // a first radius from the neighbours along the curve (simple_knn.cu:163-165), this end among them
-    const int lo = max(0, idx - 3), hi = min(nv - 1, idx + 3);
-    for (int i = lo; i <= hi; i++) {
-      const float4 q = sorted[i];
-      mag_insert(best, mag_dist2(me, q), (int)__float_as_uint(q.w));
-    }
-  }
-  const float reject = best.d[2];
-  mag_clear(best);
-  const int shift = 30 - 3 * L;
-  auto walk_cell = [&](uint32_t c) {
-    const uint4 h0 = *(const uint4*)(cells + 8 * (size_t)c), h1 = *(const uint4*)(cells + 8 * (size_t)c + 4);
-    if (h0.x >= h0.y || h0.y > (uint32_t)nv) return;                  // empty
-    const float bx[6] = {funkey((int)h0.z), funkey((int)h0.w), funkey((int)h1.x), funkey((int)h1.y), funkey((int)h1.z), funkey((int)h1.w)};
-    const float dist = box_point_dist2(bx, me.x, me.y, me.z);
-    if (dist > reject || dist > best.d[2]) return;                    // (an equal distance is walked: the tie may have the smaller position)
-    for (uint32_t i = h0.x; i < h0.y; i++) {
-      const float4 q = sorted[i];
-      mag_insert(best, mag_dist2(me, q), (int)__float_as_uint(q.w));
-    }
-  };
-  const uint32_t own = code >> shift;
-  walk_cell(own);
-  const float r2 = fminf(reject, best.d[2]);
-  const float r = sqrtf(r2) * 1.000001f;
-  const int cshift = 10 - L;
-  int lo[3], hi[3];
-  const float pc[3] = {me.x, me.y, me.z};
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const float mn = smm[k], mx = smm[3 + k];
-    lo[k] = (int)(min(f2u_sat(((pc[k] - r - mn) / (mx - mn)) * 1023), 1023u) >> cshift);
-    hi[k] = (int)(min(f2u_sat(((pc[k] + r - mn) / (mx - mn)) * 1023), 1023u) >> cshift);
-    if (!(r < FLT_MAX)) { lo[k] = 0; hi[k] = (1 << L) - 1; }            // (fewer than three comparable ends: no radius)
-  }
-  for (int cz = lo[2]; cz <= hi[2]; cz++)
-    for (int cy = lo[1]; cy <= hi[1]; cy++)
-      for (int cx = lo[0]; cx <= hi[0]; cx++) {
-        const uint32_t c = (prep_morton((uint32_t)cx << cshift) | (prep_morton((uint32_t)cy << cshift) << 1) |
-                            (prep_morton((uint32_t)cz << cshift) << 2)) >> shift;
-        if (c != own) walk_cell(c);
-      }
-  part[mypos] = best;
-}
+// the three smallest (distance, position) pairs, the end itself among them: mag_insert makes the triple independent of the traversal
+struct MagBest : Best3 {
+  typedef Best3 Out;          // part[position] = the triple
+  static constexpr bool kSelf = true, kGuarded = true;
+  __device__ __forceinline__ void clear() { best3_clear(*this); }
+  __device__ __forceinline__ float third() const { return d[2]; }
+  __device__ __forceinline__ void add(float dist, uint32_t pos) { mag_insert(*this, dist, (int)pos); }
+  __device__ __forceinline__ void store(Best3* __restrict__ part, const float4& me) const { part[__float_as_uint(me.w)] = *this; }
+};
 
 // ---- select: merge the partial triples, statements (c)-(e), per-workgroup sums of the mean
 __global__ __launch_bounds__(256) void mag_select_kernel(int n, int E, int S, const int* __restrict__ counts,
-                                                         const int2* __restrict__ cmeta, const MagTriple* __restrict__ part,
+                                                         const int2* __restrict__ cmeta, const Best3* __restrict__ part,
                                                          const float* __restrict__ ep, const int* __restrict__ mapping, float min_val,
                                                          int* __restrict__ sel, float* __restrict__ sq, int* __restrict__ nn_idx,
                                                          float* __restrict__ nn_d2, double* __restrict__ blk_sum,
@@ -341,13 +212,13 @@ __global__ __launch_bounds__(256) void mag_select_kernel(int n, int E, int S, co
   double contrib = 0.0;
   int kept = 0;
   if (a < n) {
-    MagTriple t;
-    mag_clear(t);
+    Best3 t;
+    best3_clear(t);
     int chosen = -1, eidx = -1;
     float s = 0.f;
     if (a < nv) {
       for (int y = 0; y < S; y++) {
-        const MagTriple p = part[(size_t)y * n + a];
+        const Best3 p = part[(size_t)y * n + a];
 #pragma unroll
         for (int j = 0; j < 3; j++)
           if (p.i[j] >= 0 && p.i[j] < nv) mag_insert(t, p.d[j], p.i[j]);
@@ -527,14 +398,15 @@ extern "C" int hgs_magnet_forward(void* stream, int E, int n, const float* endpo
     int S = 1;
     if (mag_use_grid(n)) {
       const size_t Npad = pad_pow2((size_t)n);
-      const int L = mag_level((size_t)n);
+      const int L = cellgrid_level((size_t)n);
       const unsigned n_cells = 1u << (3 * L);
-      hipLaunchKernelGGL(mag_morton_kernel, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, st, n, (int)Npad, s.counts, s.cpts, s.keys);
+      const MagSource src{s.counts};
+      hipLaunchKernelGGL((cellgrid_keys_kernel<MagSource, float4>), dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, st, src, n, (int)Npad, s.cpts, s.keys);
       keysort_launch(st, s.keys, Npad);
-      hipLaunchKernelGGL(mag_gather_kernel, dim3(nb), dim3(256), 0, st, n, s.counts, s.cpts, s.keys, s.sorted);
+      hipLaunchKernelGGL((cellgrid_gather_kernel<MagSource, float4>), dim3(nb), dim3(256), 0, st, src, n, s.cpts, s.keys, s.sorted);
       hipLaunchKernelGGL(cells_clear_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, st, n_cells, s.cells);
-      hipLaunchKernelGGL(mag_cells_mark_kernel, dim3(nb), dim3(256), 0, st, n, 30 - 3 * L, s.counts, s.keys, s.sorted, s.cells);
-      hipLaunchKernelGGL(mag_grid_kernel, dim3(nb), dim3(256), 0, st, n, L, s.counts, s.sorted, s.keys, s.cells, s.part);
+      hipLaunchKernelGGL(cellgrid_mark_kernel<MagSource>, dim3(nb), dim3(256), 0, st, src, n, 30 - 3 * L, s.keys, s.sorted, s.cells);
+      hipLaunchKernelGGL((cellgrid_search_kernel<MagSource, MagBest>), dim3(nb), dim3(256), 0, st, n, L, src, s.sorted, s.keys, s.cells, s.part);
     } else {
       S = mag_splits(n);
       const int chunk = ((nb + S - 1) / S) * 256;

@@ -149,11 +149,6 @@ __device__ __forceinline__ void kv_clean64(double& d, int& i, int lane) {      /
 #pragma unroll
   for (int j = 32; j > 0; j >>= 1) kv_cex(d, i, lane, j, true);
 }
-__device__ __forceinline__ double wave_sum(double v) {       // the same bits in every lane: each step adds the two halves of a pair
-#pragma unroll
-  for (int j = 32; j > 0; j >>= 1) v = v + __shfl_xor(v, j, 64);
-  return v;
-}
 __device__ __forceinline__ double uniform_f64(double v) {    // a value that is the same in every lane, moved to scalar registers
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }

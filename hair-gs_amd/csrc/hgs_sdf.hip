@@ -25,10 +25,6 @@ namespace {
 #define SDF_WAVES (SDF_BLOCK / HGS_WAVE)
 #define SDF_TILE 256                 // faces per LDS tile: 256 * 9 * 8 = 18 KiB
 
-__device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) {
-  return (ax * bx + ay * by) + az * bz;
-}
-
 __global__ __launch_bounds__(SDF_BLOCK) void mesh_sdf_kernel(int F, const double* __restrict__ tris, double ox, double oy, double oz,
                                                              double h, int nx, int ny, long long N, float* __restrict__ phi,
                                                              double* __restrict__ winding) {
@@ -96,11 +92,6 @@ __global__ __launch_bounds__(SDF_BLOCK) void mesh_sdf_kernel(int F, const double
   if (w > 0.5 && v != 0.f) v = -v;                                         // (a zero is stored as +0)
   phi[node] = v;
   if (winding) winding[node] = w;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int off = HGS_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
 }
 
 __global__ __launch_bounds__(SDF_BLOCK) void head_penalty_kernel(int E, const float* __restrict__ points, const float* __restrict__ phi,

@@ -28,10 +28,6 @@ namespace {
 #define TRACE_BLOCK 256
 #define FIXED_ONE 4294967296.0       // 2^32
 
-__device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) {
-  return (ax * bx + ay * by) + az * bz;
-}
-
 __device__ __forceinline__ bool finite3(double x, double y, double z) {
   const double big = __builtin_inf();
   return fabs(x) < big && fabs(y) < big && fabs(z) < big;

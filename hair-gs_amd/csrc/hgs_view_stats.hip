@@ -26,11 +26,6 @@ namespace {
 #define VS_PIX_PER_LANE 16          // target pixels per lane: the block count follows from it
 #define VS_MAX_BLOCKS 1024
 
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int off = HGS_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 __global__ __launch_bounds__(VS_BLOCK) void view_stats_kernel(int HW, int nb, const float* __restrict__ pred, const float* __restrict__ gt,
                                                               const uint8_t* __restrict__ mask, const float* __restrict__ fg, float fg_th,
                                                               const float* __restrict__ omap, const float* __restrict__ viewmats,

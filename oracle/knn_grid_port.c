@@ -1,7 +1,8 @@
 /*
  * knn_grid_port.c -- CPU port of distCUDA2's search over a grid of Morton cells (hair-gs_amd/csrc/hgs_knn.hip: minmax_kernel,
- * morton_kernel, gather_kernel, cells_mark_kernel, mean_dist_kernel; csrc/hgs_keysort.h), statement by statement in the same
- * float32 arithmetic (built with -ffp-contract=off), one loop iteration per lane.
+ * KnnSource, KnnBest; csrc/hgs_cellgrid.h: cellgrid_level, cellgrid_keys_kernel, cellgrid_gather_kernel, cellgrid_mark_kernel,
+ * cellgrid_search_kernel), statement by statement in the same float32 arithmetic (built with -ffp-contract=off), one loop
+ * iteration per lane.
  *
  * TEST INFRASTRUCTURE ONLY.  It exists to show, without a GPU, which input catches which decision of the search:
  * `flags` switches single decisions off (tests/test_knn_hard_cpu.py).  As written (flags = 0) it equals the brute force bit
@@ -54,7 +55,7 @@ static int cmp_key(const void* a, const void* b) {
   const uint64_t x = *(const uint64_t*)a, y = *(const uint64_t*)b;
   return x < y ? -1 : x > y;
 }
-static int knn_level(size_t P) {
+static int cellgrid_level(size_t P) {
   int L = 1;
   while (L < 7 && ((size_t)1 << (3 * (L + 1))) * 16 <= P) L++;
   return L;
@@ -101,7 +102,7 @@ void hgs_oracle_dist2_grid(int P, const float* pts, float* out, int flags, int64
     const Sorted s = {pts[3 * (size_t)id], pts[3 * (size_t)id + 1], pts[3 * (size_t)id + 2], id};
     sorted[i] = s;
   }
-  const int L = knn_level((size_t)P), shift = 30 - 3 * L, cshift = 10 - L;
+  const int L = cellgrid_level((size_t)P), shift = 30 - 3 * L, cshift = 10 - L;
   const uint32_t n_cells = 1u << (3 * L);
   uint32_t* cells = (uint32_t*)malloc(32 * (size_t)n_cells);
   for (uint32_t c = 0; c < n_cells; c++) {

@@ -152,7 +152,7 @@ SMALL = {"plane_z0": 4000, "plane_off": 4000, "line": 3000, "all_same": 300, "al
          "clusters": 6005, "lattice_holes": 4500, "aniso": 4000, "octants": 9000, "dup3": 3000, "dup5": 8500, "tiny": 3000,
          "strands": 5000, "non_finite": 3000}
 NAMES = list(FAMILIES)
-# where knn_level changes the grid (1024, 8192, 65536), one below each; 8192 and 65536 are exact pad_pow2 sizes as well
+# where cellgrid_level (csrc/hgs_cellgrid.h) changes the grid (1024, 8192, 65536), one below each; 8192 and 65536 are exact pad_pow2 sizes as well
 LARGE_SIZES = (1023, 1024, 8191, 8192, 65535, 65536)
 LARGE_FAMILIES = ("octants", "strands", "clusters", "far_small")
 

@@ -150,6 +150,24 @@ def cases():
 NAMES = list(cases())
 
 
+# where the grid path's level changes (csrc/hgs_cellgrid.h cellgrid_level: L = 1 below 1024 ends, 2 below 8192, then 3), one
+# below each, on two families of tests/knn_cases.py
+LEVEL_EDGE_SIZES = (1023, 1024, 8191, 8192)
+LEVEL_EDGE_FAMILIES = ("octants", "clusters")
+
+
+def level_edge(family, n):
+    """[S, 3, 3], S = ceil(n / 2): the points of the knn_cases family as strand ends -- strand k runs from point 2 k through a
+    middle vertex 0.02 from it to point 2 k + 1, so every end segment is far longer than min_val and every end is valid.  A set
+    of chains has an even number of ends: for an odd n tests/magnet_reference.level_edge_model takes the last end out."""
+    from tests import knn_cases as KC
+    S = (n + 1) // 2
+    ends = KC.large(family, 2 * S).reshape(S, 2, 3)
+    d = _rng(31).normal(size=(S, 3))
+    mid = ends[:, 0] + 0.02 * d / np.linalg.norm(d, axis=1, keepdims=True)
+    return np.stack([ends[:, 0], mid, ends[:, 1]], 1).astype(np.float32)
+
+
 def big_clustered():
     """20 000 ends clustered like strand_polylines(10000, 1): the grid path at a size where it is the automatic choice."""
     from synthetic import strand_polylines

@@ -27,6 +27,19 @@ def model_of(pts, device="cpu"):
     return HairGaussianModel.from_strands(pts, device=device)
 
 
+def level_edge_model(pts, n, device="cpu"):
+    """The model of tests/magnet_cases.level_edge(family, n) with exactly n ends.  For an odd n the last segment of the last
+    strand is re-attached to endpoint 1 (the middle vertex of strand 0, then of degree 3): the last strand's tip is in no
+    segment any more, and the list of ends is the first n of the family's n + 1 points.  The degree-3 vertex is deliberate and
+    inert: the term reads the degree-1 endpoints and each one's segment partner, nothing else of the topology, and a set of
+    chains cannot have an odd number of ends.  (Collapsing an end segment instead would leave n + 1 ends in the table, and the
+    grid's level is chosen from the table's size: 1023 would run at the level of 1024.)"""
+    m = model_of(pts, device)
+    if n % 2:
+        m.endpoint_pairs[-1, 1] = 1
+    return m
+
+
 def topology(model):
     """(ends, partner, mapping) as the statement builds them (:134-138), numpy int64."""
     E = model._endpoints.shape[0]

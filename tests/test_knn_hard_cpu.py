@@ -76,7 +76,7 @@ def test_non_finite_points_are_invisible_to_the_others():
 
 
 def test_margin_cloud_needs_the_margin_of_the_cube_range():
-    """What KC.margin_cloud() claims, in the arithmetic of mean_dist_kernel / morton_kernel (csrc/hgs_knn.hip): without the
+    """What KC.margin_cloud() claims, in the arithmetic of cellgrid_search_kernel / cellgrid_code (csrc/hgs_cellgrid.h): without the
     1.000001 the cube range of point 0 stops one cell short of its third neighbour, and the mean changes."""
     f = np.float32
     p = KC.margin_cloud()

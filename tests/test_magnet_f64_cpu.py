@@ -47,6 +47,19 @@ def test_case_list_covers_what_the_term_can_meet():
     assert _ref("one_strand").r64.rows == 0 and _ref("no_strands").r64.rows == 0   # the n < 3 rules
 
 
+@pytest.mark.parametrize("n", MC.LEVEL_EDGE_SIZES)
+@pytest.mark.parametrize("family", MC.LEVEL_EDGE_FAMILIES)
+def test_level_edge_inputs_have_n_valid_ends(family, n):
+    """The inputs of tests/test_magnet_gpu.py::test_grid_path_where_its_level_changes really straddle the level edges: the
+    table holds exactly n ends (the grid's level is chosen from that number) and at least n - 1 of them are valid."""
+    m = MR.level_edge_model(MC.level_edge(family, n), n)
+    ends, partner, _ = MR.topology(m)
+    ep = m._endpoints.detach()
+    valid = torch.norm(ep[ends] - ep[partner], dim=1) > m.min_val
+    assert len(ends) == n and int(valid.sum()) >= n - 1
+    assert np.isfinite(ep.numpy()).all()
+
+
 @pytest.mark.parametrize("name", MC.NAMES)
 def test_fp32_statement_is_the_projects_and_selects_like_float64(name):
     """tests/magnet_reference.torch_statement IS strand_joints_magnet_loss (same bits), and in float32 it selects the same

@@ -108,6 +108,23 @@ def test_grid_path_at_20000_clustered_ends():
     _same_bits(g, auto)
 
 
+@pytest.mark.parametrize("n", MC.LEVEL_EDGE_SIZES)
+@pytest.mark.parametrize("family", MC.LEVEL_EDGE_FAMILIES)
+def test_grid_path_where_its_level_changes(family, n):
+    """n ends on both sides of the sizes at which the grid takes its next level (1024: L = 2, 8192: L = 3;
+    tests/test_magnet_f64_cpu.py checks that the inputs have n ends, all valid): forced grid against forced tiles bit for bit
+    in everything, neighbours and squared distances against hgs_knn3's route bit for bit."""
+    model = MR.level_edge_model(MC.level_edge(family, n), n, "cuda")
+    g = _run(model, GRID)
+    _same_bits(_run(model, TILES), g)
+    route, seen = _knn3_route(model)
+    nv = g["nv"]
+    assert g["n"] == n and nv == route.nv and g["rows"] == route.rows and nv >= n - 1
+    np.testing.assert_array_equal(g["nn_idx"][:nv], seen["idx"])
+    assert g["nn_d2"][:nv].tobytes() == seen["d2"].astype(np.float32).tobytes()
+    np.testing.assert_array_equal(g["sel"][:nv, 0], route.sel)
+
+
 def _tiny(lambda_magnet, fused_magnet, perturb=True):
     from arguments import OptimizationParams
     from synthetic import build_workload

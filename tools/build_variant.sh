@@ -8,8 +8,8 @@ name=$1; units=${2//,/ }; shift 2
 make -s -C $CS
 objs=$(ls $CS/build/*.o)
 for unit in $units; do
-  contract=-ffp-contract=fast-honor-pragmas
-  case $unit in hgs_api|hgs_preprocess|hgs_binning|hgs_knn) contract=-ffp-contract=off;; esac
+  contract=-ffp-contract=off                # (as csrc/Makefile: every unit is STRICT but the four RELAXED ones)
+  case $unit in hgs_blend|hgs_losses|hgs_strands|hgs_optim) contract=-ffp-contract=fast-honor-pragmas;; esac
   noslp=
   case $unit in hgs_blend|hgs_losses|hgs_preprocess) noslp=-fno-slp-vectorize;; esac     # (as csrc/Makefile)
   hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -fno-fast-math -munsafe-fp-atomics -Wall -Wno-unused-function $contract $noslp "$@" -c $CS/$unit.hip -o /tmp/variant_${name}_$unit.o
