@@ -5,6 +5,8 @@ merge.py that the reference leaves to scripts/convert_output.py (MeshLab PLYs of
                            [--points 100] [--min_segments 1] [--min_length 0] [--max_root_distance D] [--colour model|strand]
                            [--device cuda|cpu] [--interpolate [--roots N] [--guides 4] [--max_guide_distance D] [--max_angle 60] [--no_guides]]
                            [--resolve_head [--head_margin 0] [--collide_iters 8] [--head_sdf PATH]]
+                           [--attach_roots [--attach_margin 0] [--attach_step S] [--attach_max_steps 256] [--attach_pull 1] [--attach_descent 0.25]
+                            [--attach_max_distance D] [--attach_field PATH] [--attach_min_conf 0.5] [--attach_scalp_distance D] [--drop_unattached]]
 A model directory is read at its newest point_cloud/iteration_N (utils/system.py model_ply, as eval.py reads it); the SH degree is read off the file.  Every
 strand is resampled by arc length to --points points (0: its joints as they are) with per-point colour, opacity and width
 (scene/strand_export.py: the contract; --device cuda = the HIP kernels on the model's device tensors, cpu = the numpy path), strands
@@ -28,7 +30,20 @@ and --interpolate, before the writers, a joint closer to the head than --head_ma
 moved out along the gradient of the capture's distance field -- --head_sdf, by default <-s>/head_sdf.npz, which head_sdf.py writes --
 in at most --collide_iters pushes (1 to 32), and the joints behind it keep their segments' lengths and return to their path.  Roots do
 not move and attributes are untouched; the points inside before and after, the points moved, those left inside and the largest
-displacement are printed.  It works on ragged strands (--points 0) too.  Without the flag the strands are written as they are."""
+displacement are printed.  It works on ragged strands (--points 0) too.  Without the flag the strands are written as they are.
+--attach_roots roots every strand on the head (scene/strand_attach.py: the contract): trained strands begin wherever a view saw hair,
+millimetres to centimetres above the skin.  After the resampling and its filters, before --interpolate and --resolve_head (guides are
+rooted before they are blended, and the new joints are pushed out with the rest), a polyline is marched from every strand's root joint
+back to the head of the same distance field (--head_sdf, else <-s>/head_sdf.npz): it starts along the strand's backward tangent, follows
+the direction volume --attach_field (an .npz of trace_strands.py --field) where that has at least --attach_min_conf aligned mass, and
+is pulled down the field's gradient with weight --attach_pull, never descending by less than --attach_descent of a step, in steps of
+--attach_step (half the field's spacing) and at most --attach_max_steps of them, until it lands --attach_margin above the surface.  The
+new joints are put in front of the strand's own with the root joint's attributes; with --points M > 0 the joined strand is resampled
+to M points again.  A strand already on the head, one farther than --attach_max_distance from it and one whose march fails keep all
+their bits (--drop_unattached drops the failed ones); with --attach_scalp_distance D a strand that landed farther than D from every
+strand root -- on the face or the neck -- is restored too.  The strands attached, already rooted, failed by reason and dropped, the
+joints added, the largest and mean root gap before and the largest |d - margin| of the landed roots are printed.  Without the flag
+the strands are written as they are."""
 import os
 import sys
 
@@ -127,6 +142,36 @@ def resolved(args, path, strands):
     return out
 
 
+def attach_knobs(args):
+    """--attach_roots: the march's keyword arguments (scene/strand_attach.py check_parameters)."""
+    return dict(margin=args.attach_margin, step=args.attach_step, max_steps=args.attach_max_steps, pull=args.attach_pull,
+                descent=args.attach_descent, max_distance=args.attach_max_distance, min_conf=args.attach_min_conf)
+
+
+def attached(args, path, model, strands):
+    """--attach_roots: the strands marched back to the head of the field at `path` (scene/strand_attach.py), and what that did."""
+    from scene import strand_attach as SA
+    from utils import head_sdf
+    from utils.trace import load_field
+    volume = load_field(args.attach_field) if args.attach_field is not None else None
+    scalp = {}
+    if args.attach_scalp_distance is not None:
+        scalp = dict(scalp_points=np.asarray(model.ref_strand_root, np.float64).reshape(-1, 3), scalp_distance=args.attach_scalp_distance)
+    out, rep = SA.attach_roots(strands, head_sdf.load_sdf(path), volume, points=args.points, device=None if args.device == "cpu" else args.device,
+                               **scalp, **attach_knobs(args))
+    failed = sum(rep["failed"].values())
+    dropped = 0
+    if args.drop_unattached and failed:
+        out = SA.select_strands(out, (rep["reason"] == SA.REACHED) | (rep["reason"] == SA.NEAR))
+        dropped = failed
+    reasons = ", ".join(f"{k} {v}" for k, v in rep["failed"].items())
+    print(f"Attached to the head ({path}, margin {args.attach_margin:g}" + (f", steered by {args.attach_field}" if volume is not None else "")
+          + f"): {rep['attached']} of {rep['strands']} strands attached, {rep['near']} already rooted, {failed} failed"
+          + (f" ({reasons})" if failed else "") + f", {dropped} dropped; {rep['joints_added']} joints added; root gap before: largest "
+          f"{rep['gap_max']:.4g}, mean {rep['gap_mean']:.4g}; largest |d - margin| of the landed roots: {rep['landed_error']:.3g}")
+    return out
+
+
 def main(argv=None):
     parser = ArgumentParser(description="Export the strands of a trained model as hair assets")
     parser.add_argument("--model_path", "-m", required=True, help="a strand model PLY, or a model directory")
@@ -149,8 +194,39 @@ def main(argv=None):
     parser.add_argument("--head_margin", type=float, default=0.0, help="with --resolve_head: keep the joints this far outside the head")
     parser.add_argument("--collide_iters", type=int, default=8, help="with --resolve_head: pushes per joint at most (1 to 32)")
     parser.add_argument("--head_sdf", default=None, help="with --resolve_head: the head's distance field; default: <source_path>/head_sdf.npz")
+    parser.add_argument("--attach_roots", action="store_true", help="march every strand's root back to the head and prepend the new joints")
+    parser.add_argument("--attach_margin", type=float, default=0.0, help="with --attach_roots: target distance above the head surface")
+    parser.add_argument("--attach_step", type=float, default=None, help="with --attach_roots: march step length; default: half the field's spacing")
+    parser.add_argument("--attach_max_steps", type=int, default=256, help="with --attach_roots: steps per strand at most (1 to 1024)")
+    parser.add_argument("--attach_pull", type=float, default=1.0, help="with --attach_roots: weight of the pull toward the head")
+    parser.add_argument("--attach_descent", type=float, default=0.25, help="with --attach_roots: least cosine between a step and the way down (above 0, at most 1)")
+    parser.add_argument("--attach_max_distance", type=float, default=None, help="with --attach_roots: strands starting farther than this from the head stay as they are")
+    parser.add_argument("--attach_field", default=None, help="with --attach_roots: the direction volume (an .npz of trace_strands.py --field) that steers the march")
+    parser.add_argument("--attach_min_conf", type=float, default=0.5, help="with --attach_roots: least aligned mass the volume must have at a point to steer")
+    parser.add_argument("--attach_scalp_distance", type=float, default=None, help="with --attach_roots: a landed root farther than this from every strand root is off the scalp; its strand is restored")
+    parser.add_argument("--drop_unattached", action="store_true", help="with --attach_roots: drop the strands whose march failed (default: write them unchanged)")
     args = parser.parse_args(argv)
     field = None
+    if args.attach_roots:
+        from scene.strand_attach import MAX_STEPS as ATTACH_MAX_STEPS
+        for flag, value, good, words in (
+                ("--attach_margin", args.attach_margin, np.isfinite(args.attach_margin) and args.attach_margin >= 0.0, "a finite distance >= 0"),
+                ("--attach_step", args.attach_step, args.attach_step is None or (np.isfinite(args.attach_step) and args.attach_step > 0.0), "a finite length > 0"),
+                ("--attach_max_steps", args.attach_max_steps, 1 <= args.attach_max_steps <= ATTACH_MAX_STEPS, f"1 to {ATTACH_MAX_STEPS}"),
+                ("--attach_pull", args.attach_pull, np.isfinite(args.attach_pull) and args.attach_pull >= 0.0, "a finite weight >= 0"),
+                ("--attach_descent", args.attach_descent, 0.0 < args.attach_descent <= 1.0, "above 0, at most 1"),
+                ("--attach_max_distance", args.attach_max_distance, args.attach_max_distance is None or args.attach_max_distance >= 0.0, "a distance >= 0"),
+                ("--attach_min_conf", args.attach_min_conf, np.isfinite(args.attach_min_conf), "a finite mass"),
+                ("--attach_scalp_distance", args.attach_scalp_distance, args.attach_scalp_distance is None or args.attach_scalp_distance >= 0.0, "a distance >= 0"),
+                ("--attach_field", args.attach_field, args.attach_field is None or os.path.exists(args.attach_field), "no such file")):
+            if not good:
+                parser.exit(2, f"export_strands.py: {flag} {value}: {words}\n")
+        field = head_field_path(args)
+        if field is None:
+            parser.exit(2, "export_strands.py: --attach_roots needs the head's distance field and found none"
+                           + (f" at {args.head_sdf}" if args.head_sdf is not None else
+                              f" at {os.path.join(args.source_path, 'head_sdf.npz')}" if args.source_path is not None else " (no -s and no --head_sdf)")
+                           + ": run head_sdf.py on the capture, or name a field with --head_sdf\n")
     if args.resolve_head:
         if not (np.isfinite(args.head_margin) and args.head_margin >= 0.0):
             parser.exit(2, f"export_strands.py: --head_margin {args.head_margin}: a finite distance >= 0\n")
@@ -176,6 +252,8 @@ def main(argv=None):
                               max_root_distance=args.max_root_distance, device=None if args.device == "cpu" else args.device)
     print(f"Strands: {model.strands_info.n_strands}, kept: {result.n_strands}, points: {result.points.shape[0]}"
           + (f" ({args.points} per strand)" if args.points else " (the joints)"))
+    if args.attach_roots:
+        result = attached(args, field, model, result)
     if args.interpolate:
         result = interpolated(args, model, result)
     if args.resolve_head:

@@ -112,6 +112,10 @@ SIGNATURES = {
     "hgs_head_penalty_forward": (ci, [vp, ci, vp, vp, ci, ci, ci, cf, cf, cf, cf, cf, vp, vp, vp, vp, vp]),
     "hgs_head_penalty_backward": (ci, [vp, ci, vp, vp, vp]),
     "hgs_strand_collide": (ci, [vp, ci, vp, C.c_longlong, vp, vp, ci, ci, ci, cf, cf, cf, cf, cf, cf, ci, vp, vp, vp]),
+    "hgs_root_attach": (ci, [vp, ci, vp, C.c_longlong, vp, vp, ci, ci, ci, cf, cf, cf, cf, vp, vp, ci, ci, ci, C.c_double, C.c_double,
+                             C.c_double, C.c_double, C.c_double, cf, cf, C.c_double, ci, ci, C.c_double, C.c_double, C.c_double, vp, vp, vp,
+                             vp]),
+    "hgs_strand_rejoin": (ci, [vp, ci, vp, C.c_longlong, vp, vp, ci, vp, ci, vp, vp, ci, vp, C.c_longlong, vp, vp]),
     "hgs_field_splat": (ci, [vp, ci, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, C.c_double, vp, vp]),
     "hgs_field_solve": (ci, [vp, ci, ci, ci, vp, vp, vp]),
     "hgs_strand_trace": (ci, [vp, ci, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, C.c_double, ci,

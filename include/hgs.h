@@ -978,6 +978,47 @@ int hgs_strand_collide(void* stream, int K, const long long* offsets, long long 
                        int nz, float ox, float oy, float oz, float inv_h, float margin, float skin, int iters, float* out_points,
                        int* moved, int* unresolved);
 
+/* hgs_root_attach, hgs_strand_rejoin (csrc/hgs_attach.hip) <-> exported strands rooted on the head (scene/strand_attach.py states the
+ *   contract and has the numpy path; export_strands.py --attach_roots; the reference has nothing of the kind).  Added under ABI 15.
+ *   Strands as for hgs_strand_collide: K strands over points [P][3] float32 through offsets [K + 1] int64 (the caller's duty; a range
+ *   that does not lie inside the P points counts as a strand without joints).  The head's field phi as for hgs_strand_collide,
+ *   sampled by S(x) = csrc/hgs_sdf_sample.h at float32(x): (ok, d, G).  The direction volume (vol_dir [vnz][vny][vnx][3], vol_conf
+ *   [vnz][vny][vnx] float64 on the grid origin + index * vh, 2 to 1024 nodes an axis, at most 2^26 in all) may be null (both
+ *   pointers): it is sampled by hgs_strand_trace's corner loop at t = (x - origin) * (1 / vh), signs chosen against p.
+ * hgs_root_attach: per strand with joints p_0 .. p_{n-1}, float64, one rounding per operation, dot(u, v) = (u0*v0 + u1*v1) + u2*v2;
+ *   m = (double)margin, tl = (double)tol:
+ *     n < 2: DEGENERATE.  x = p_0; (ok, d, G) = S(x).  not ok: RANGE.  d <= m + tl: NEAR.  d - m > max_distance: FAR.
+ *     e = x - p_1, le = sqrt(dot(e, e)); p = e / le where le is finite and > 0, else -G / sqrt(dot(G, G)).
+ *     at most max_steps (1 to 1024) times:
+ *       gn = sqrt(dot(G, G)); unless finite and > 0: FLAT
+ *       if d - m <= step: at most land_iters (1 to 8) times: c = (m - d) / gn; x = x + (c * G) / gn; (ok, d, G) = S(x); not ok: RANGE;
+ *         |d - m| <= tl: append x, REACHED; gn = sqrt(dot(G, G)); unless finite and > 0: FLAT.  Then UNLANDED.
+ *       nrm = -G / gn; f = the volume's direction v / sqrt(dot(v, v)) where there is a volume, x is in its range, w >= min_conf and
+ *       dot(v, v) is finite and > 0, else p; v = f + pull * nrm; dd = v / sqrt(dot(v, v)) where that length is finite and > 0, else
+ *       nrm; dot(dd, nrm) < descent: dd = nrm; x = x + step * dd; p = dd; append x; (ok, d, G) = S(x); not ok: RANGE.
+ *     then STEPS.
+ *   ext [K][max_steps + 1][3] float64 receives the appended points in order (rows from count on are unspecified), count [K] int32
+ *   their number, reason [K] int32: 0 reached, 1 near, 2 degenerate, 3 range, 4 flat, 5 steps, 6 unlanded, 7 far; landed [K] float32
+ *   the distance d at the landed point (reached) or at the root (near), +inf otherwise.  margin, tol: finite, >= 0; step finite and
+ *   > 0; pull finite and >= 0; 0 < descent <= 1; max_distance >= 0, may be +inf; min_conf finite.  One lane per strand, no atomics.
+ * hgs_strand_rejoin: attrs [P][C] float32 (0 <= C <= 64), ext / count / reason as above with ext_rows = max_steps + 1 rows a strand,
+ *   out_offsets [K + 1] int64 made by the caller: a strand that is not reached (reason != 0) owns n output points and is copied; a
+ *   reached one owns count + n points with M == 0 -- float32(ext[count - 1]), .., float32(ext[0]), then p_0 .. p_{n-1}, the new joints
+ *   with p_0's attributes -- and M points with M >= 2: that polyline resampled by arc length by hgs_strand_resample's statement
+ *   (len_i and cum in float64 in segment order, t = (j / (M - 1)) L, the largest i <= m - 2 with cum_i <= t or 0 where there is none,
+ *   w = (t - cum_i) / len_i or 0 unless len_i > 0, v_i + w (v_{i+1} - v_i), the same for the joints' own attributes, rounded once; the
+ *   end samples are the end joints' bits).  A strand whose output range is not the size this asks for, or does not lie inside the
+ *   n_out points, is not written.  out_points [n_out][3] and out_attrs [n_out][C] must not alias the inputs.
+ *   Both: bad sizes and parameters and, for K > 0, null or aliased pointers return 1 before anything is launched; K == 0 returns 0. */
+int hgs_root_attach(void* stream, int K, const long long* offsets, long long P, const float* points, const float* phi, int nx, int ny,
+                    int nz, float ox, float oy, float oz, float inv_h, const double* vol_dir, const double* vol_conf, int vnx, int vny,
+                    int vnz, double vox, double voy, double voz, double vh, double min_conf, float margin, float tol, double step,
+                    int max_steps, int land_iters, double pull, double descent, double max_distance, double* ext, int* count,
+                    int* reason, float* landed);
+int hgs_strand_rejoin(void* stream, int K, const long long* offsets, long long P, const float* points, const float* attrs, int C,
+                      const double* ext, int ext_rows, const int* count, const int* reason, int M, const long long* out_offsets,
+                      long long n_out, float* out_points, float* out_attrs);
+
 /* Strands traced from the scalp through the lifted hair directions (csrc/hgs_trace.hip; utils/trace.py states the contract and has
  *   the numpy paths).  All float64, one rounding per operation.  Every argument is checked before a pointer is touched.  The grid:
  *   node (ix, iy, iz) lies at origin + index * h, 2 <= n <= 1024 an axis, at most 2^26 nodes in all.
