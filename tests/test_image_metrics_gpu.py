@@ -1,5 +1,6 @@
 """Image metrics on the GPU (hair-gs_amd/csrc/hgs_view_stats.hip through loss/image_metrics.py, and view_metrics.py): the kernel
-against the CPU path on random planes for every combination of absent planes, bitwise reproducibility and batch independence,
+against the CPU path on random planes for every combination of absent planes (the within counts may differ only by the
+pixels the float64 reference calls ambiguous), bitwise reproducibility and batch independence,
 and the driver end to end on a trained Stage-I cloud and on the strand model merge.py makes from it."""
 import itertools
 import json
@@ -48,6 +49,19 @@ def _subset(p, fg, mask, omap, conf):
     return kw
 
 
+def _ambiguous(p, with_mask):
+    """Per view, the number of orientation pixels within the float64 reference's margin of the 10 and of the 20 degree edge
+    (tests/view_stats_reference.py): only there may two float32 evaluations count differently."""
+    from loss.image_metrics import MIN_VAL
+    from tests import view_stats_reference as VR
+    res = []
+    for v in range(p["omap"].shape[0]):
+        omap = p["omap"][v].numpy()
+        om = p["gt_mask"][v].numpy() if with_mask else (omap != 0).any(axis=0)
+        res.append(VR.ambiguous_counts(omap, p["viewmats"][v].numpy(), MIN_VAL, p["gt_theta"][v].numpy(), om))
+    return res
+
+
 def _rel(a, b):
     return abs(a - b) / max(abs(b), 1e-300)
 
@@ -56,12 +70,13 @@ def _rel(a, b):
 def test_kernel_matches_the_cpu_path(V, H, W):
     from loss.image_metrics import view_metrics
     p = _planes(V, H, W, seed=H)
+    allowed = {mask: _ambiguous(p, mask) for mask in (False, True)}
     worst = 0
     for fg, mask, omap, conf in itertools.product((False, True), repeat=4):
         kw = _subset(p, fg, mask, omap, conf)
         cpu = view_metrics(**kw)
         gpu = view_metrics(**{k: v.cuda() for k, v in kw.items()})
-        for c, g in zip(cpu, gpu):
+        for v, (c, g) in enumerate(zip(cpu, gpu)):
             assert {k for k, v in c.items() if v is None} == {k for k, v in g.items() if v is None}
             for k in COUNTS:
                 assert c[k] == g[k], (k, fg, mask, omap, conf)
@@ -72,10 +87,10 @@ def test_kernel_matches_the_cpu_path(V, H, W):
                 if c[k] is not None:
                     assert c[k] == g[k] or _rel(g[k], c[k]) <= 1e-5, (k, c[k], g[k])
             if c["orient_count"] is not None:
-                for k in ("orient_within_10_count", "orient_within_20_count"):
+                for k, amb in zip(("orient_within_10_count", "orient_within_20_count"), allowed[mask][v]):
                     d = abs(c[k] - g[k])
                     worst = max(worst, d)
-                    assert d <= 1e-4 * c["orient_count"], (k, c[k], g[k])
+                    assert d <= amb, (k, c[k], g[k], amb)
             assert abs(c["ssim"] - g["ssim"]) <= 2e-5 and abs(c["l1"] - g["l1"]) <= 2e-5
             assert c["psnr"] == g["psnr"] or abs(c["psnr"] - g["psnr"]) <= 1e-9
     print(f"V={V} {H}x{W}: largest within-count difference {worst}")
