@@ -80,6 +80,9 @@ class OptimizationParams(ParamGroup):
         # the head-penetration term of a strand model (utils/head_sdf.py; off by default): its weight, and how far outside the head's
         # surface, in scene units, a joint already pays.  train.py loads <source_path>/head_sdf.npz (head_sdf.py writes it)
         ("lambda_head", 0.0, False), ("head_margin", 0.0, False),
+        # the 3-D direction term of a strand model (utils/direction_term.py; off by default): its weight, the .npz direction volume
+        # that trace_strands.py --field wrote (train.py loads it), and the interpolated confidence from which a segment takes part
+        ("lambda_direction", 0.0, False), ("direction_field", "", False), ("direction_min_conf", 0.5, False),
     )
 
     def _finalise(self):

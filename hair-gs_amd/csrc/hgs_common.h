@@ -455,7 +455,7 @@ __device__ __forceinline__ uint32_t hgs_wave_incl_scan(uint32_t v, int lane) {
   return v;
 }
 // float64 sum over the wavefront by an xor butterfly: each step adds the two halves of a pair, so every lane ends with the same
-// bits.  The association is part of the bit contracts of its users (hgs_normals.hip, hgs_view_stats.hip, hgs_sdf.hip).
+// bits.  The association is part of the bit contracts of its users (hgs_normals.hip, hgs_view_stats.hip, hgs_sdf.hip, hgs_direction.hip).
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = HGS_WAVE / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off, HGS_WAVE);

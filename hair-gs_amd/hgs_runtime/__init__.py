@@ -111,6 +111,9 @@ SIGNATURES = {
     "hgs_head_penalty_num_blocks": (ci, [ci]),
     "hgs_head_penalty_forward": (ci, [vp, ci, vp, vp, ci, ci, ci, cf, cf, cf, cf, cf, vp, vp, vp, vp, vp]),
     "hgs_head_penalty_backward": (ci, [vp, ci, vp, vp, vp]),
+    "hgs_direction_loss_num_blocks": (ci, [ci]),
+    "hgs_direction_loss_forward": (ci, [vp, ci, vp, vp, vp, ci, ci, ci, cf, cf, cf, cf, cf, vp, vp, vp, vp, vp]),
+    "hgs_direction_loss_backward": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
     "hgs_strand_collide": (ci, [vp, ci, vp, C.c_longlong, vp, vp, ci, ci, ci, cf, cf, cf, cf, cf, cf, ci, vp, vp, vp]),
     "hgs_root_attach": (ci, [vp, ci, vp, C.c_longlong, vp, vp, ci, ci, ci, cf, cf, cf, cf, vp, vp, ci, ci, ci, C.c_double, C.c_double,
                              C.c_double, C.c_double, C.c_double, cf, cf, C.c_double, ci, ci, C.c_double, C.c_double, C.c_double, vp, vp, vp,

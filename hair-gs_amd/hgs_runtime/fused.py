@@ -1,5 +1,6 @@
 """torch.autograd front-ends of the fused HIP kernels that replace PyTorch-side chains on the training-step path
-(include/hgs.h: hgs_strand_geometry_*, hgs_ssim_l1_*, hgs_orientation_loss_*, hgs_magnet_*, hgs_head_penalty_*).  GPU tensors only."""
+(include/hgs.h: hgs_strand_geometry_*, hgs_ssim_l1_*, hgs_orientation_loss_*, hgs_magnet_*, hgs_head_penalty_*,
+hgs_direction_loss_*).  GPU tensors only."""
 import ctypes as C
 import math
 
@@ -337,6 +338,115 @@ def head_penalty(points, sdf, margin, info=None, scratch=None):
     per-point penalty and interpolated distance, +inf out of range), "g" ([E, 3]: the gradient for an upstream of E).  `scratch`: a
     HeadScratch for E points that the call works in (and that the next call overwrites); None: its own."""
     return _HeadPenalty.apply(points, sdf, margin, info, scratch)
+
+
+class DirectionTable:
+    """What the direction term's device op (include/hgs.h hgs_direction_loss_*) needs of the topology, built on the host side of a
+    topology event: `pairs` (endpoint_pairs, int64 [S, 2], every entry checked to lie in [0, E) -- the kernels trust it) and the
+    incidence CSR of utils/direction_term.py, `offsets` int32 [E + 1] and `entries` int32 [2S] (2 s + side, ascending within an
+    endpoint's run), on the model's device.  DirectionTable.of(model) remembers it on the model for as long as `endpoint_pairs` is
+    the same tensor."""
+
+    def __init__(self, pairs, E):
+        pairs = rt.require_gpu_tensor(pairs, "endpoint_pairs", torch.int64)
+        if pairs.dim() != 2 or pairs.shape[1] != 2:
+            raise rt.HgsError(f"DirectionTable: endpoint_pairs {tuple(pairs.shape)}: [S, 2] expected")
+        E, S = int(E), int(pairs.shape[0])
+        if E < 0 or E > (1 << 28) or S > (1 << 28):
+            raise rt.HgsError(f"DirectionTable: {E} endpoints and {S} segments (at most 2^28 each)")
+        flat = pairs.reshape(-1)
+        if S > 0:
+            lo, hi = int(flat.min()), int(flat.max())       # (one read-back, on the host side of a topology event)
+            if lo < 0 or hi >= E:
+                raise rt.HgsError(f"DirectionTable: endpoint_pairs holds endpoint ids from {lo} to {hi}, the model has {E} endpoints")
+        self.pairs, self.E, self.S = pairs, E, S
+        self.entries = torch.sort(flat, stable=True).indices.to(torch.int32).contiguous()
+        offsets = torch.zeros(E + 1, dtype=torch.int64, device=pairs.device)
+        if S > 0:
+            offsets[1:] = torch.cumsum(torch.bincount(flat, minlength=E), dim=0)
+        self.offsets = offsets.to(torch.int32).contiguous()
+
+    @classmethod
+    def of(cls, model):
+        cached = getattr(model, "_direction_table_cache", None)
+        E = int(model._endpoints.shape[0])
+        if cached is None or cached[0] is not model.endpoint_pairs or cached[1].E != E:
+            if not model._endpoints.is_cuda:
+                raise rt.HgsError("DirectionTable: the model must live on the GPU (libhgs.so has no CPU path)")
+            cached = model._direction_table_cache = (model.endpoint_pairs, cls(model.endpoint_pairs, E))
+        return cached[1]
+
+
+class DirectionScratch:
+    """What direction_loss keeps between its forward and its backward for S segments among E endpoints: gs [S, 3], term and w [S]
+    (float32), out [2] and the forward's float64 partial sums.  The fused iteration holds one for the model's topology and replaces
+    it in refresh() after a topology event; a call without one allocates its own."""
+
+    def __init__(self, S, E, device):
+        S, E = int(S), int(E)
+        f32 = dict(dtype=torch.float32, device=device)
+        self.S, self.E = S, E
+        self.gs = torch.empty((S, 3), **f32)
+        self.term, self.w = torch.empty((S,), **f32), torch.empty((S,), **f32)
+        self.partials = torch.empty((2 * max(1, int(rt.lib().hgs_direction_loss_num_blocks(S))),), dtype=torch.float64, device=device)
+
+
+class _DirectionLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, table, volume, min_conf, info, scratch):
+        points = rt.require_gpu_tensor(points, "points", torch.float32)
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise rt.HgsError(f"direction_loss: points {tuple(points.shape)}: [E, 3] expected")
+        E, S, dev = int(points.shape[0]), table.S, points.device
+        if E != table.E or table.pairs.device != dev:
+            raise rt.HgsError(f"direction_loss: the table was built for {table.E} endpoints on {table.pairs.device}, the call has {E} on "
+                              f"{dev}: a topology event needs a new DirectionTable (FusedStrandStep.refresh())")
+        if scratch is None:
+            scratch = DirectionScratch(S, E, dev)
+        elif scratch.S != S or scratch.E != E or scratch.gs.device != dev:
+            raise rt.HgsError(f"direction_loss: the scratch was made for {scratch.S} segments among {scratch.E} endpoints on "
+                              f"{scratch.gs.device}, the call has {S} among {E} on {dev}: a topology event needs a new one "
+                              "(FusedStrandStep.refresh())")
+        vol = volume.on(dev)["vol"]
+        nx, ny, nz = volume.shape
+        if vol.numel() != 4 * nx * ny * nz:
+            raise rt.HgsError(f"direction_loss: a volume of {vol.numel()} values for a grid of {nx} x {ny} x {nz} nodes of 4")
+        out = torch.empty((2,), dtype=torch.float32, device=dev)
+        o = volume.origin32
+        with torch.cuda.device(dev):
+            rt.check(rt.lib().hgs_direction_loss_forward(rt.current_stream(), S, rt.ptr(points), rt.ptr(table.pairs), rt.ptr(vol), nx, ny,
+                                                         nz, float(o[0]), float(o[1]), float(o[2]), float(volume.inv_h32),
+                                                         float(min_conf), rt.ptr(scratch.gs), rt.ptr(scratch.term), rt.ptr(scratch.w),
+                                                         rt.ptr(scratch.partials), rt.ptr(out)))
+        ctx.scratch, ctx.table = scratch, table
+        if info is not None:
+            info.update(out=out, term=scratch.term, w=scratch.w, gs=scratch.gs)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, go):
+        scratch, table = ctx.scratch, ctx.table
+        go = go.contiguous().to(torch.float32)
+        d = torch.empty((table.E, 3), dtype=torch.float32, device=scratch.gs.device)
+        with torch.cuda.device(d.device):
+            rt.check(rt.lib().hgs_direction_loss_backward(rt.current_stream(), table.E, table.S, rt.ptr(table.offsets),
+                                                          rt.ptr(table.entries), rt.ptr(scratch.gs), rt.ptr(go), rt.ptr(d)))
+        return d, None, None, None, None, None
+
+
+def direction_loss(points, table, volume, min_conf, info=None, scratch=None):
+    """The 3-D direction term (utils/direction_term.py states it; loss.losses.strand_direction_loss is the same statement in torch
+    ops) of the segments `table` (a DirectionTable) of `points` [E, 3] against the DirectionVolume `volume` as one device op: the
+    scalar, differentiable w.r.t. points, no host synchronisation.  `info`: a dict that receives the op's other outputs (device
+    tensors, no copy): "out" ([2]: the value; the active segments as int32 bits -- direction_active reads them), "term" and "w" ([S]:
+    the per-segment sin^2 and interpolated confidence), "gs" ([S, 3]: d term / d (b - a)).  `scratch`: a DirectionScratch for the
+    table's S and E that the call works in (and that the next call overwrites); None: its own."""
+    return _DirectionLoss.apply(points, table, volume, min_conf, info, scratch)
+
+
+def direction_active(info):
+    """Segments that passed the gate in the direction_loss call that filled `info` (one read-back: tests and tools)."""
+    return int(info["out"].view(torch.int32)[1])
 
 
 class FusedAdam(torch.optim.Optimizer):

@@ -378,9 +378,9 @@ def _raster_head_forward(step, xyz, scale, quat, opacity, extra4, shs, endpoints
         d_extra.fill_(float("nan"))
     # the tail of the head's reduction rides in the backward's parameter launch (include/hgs.h HgsHeadTail)
     # (with the magnet term loss() adds to the head's total right after this forward: the total must be complete by then)
-    # (the same with the head-penetration term)
+    # (the same with the head-penetration term and with the 3-D direction term)
     hp.defer_tail = 1 if (step.defer_tail and xyz.shape[0] > 0 and getattr(step, "magnet", None) is None
-                          and getattr(step, "head_sdf", None) is None) else 0
+                          and getattr(step, "head_sdf", None) is None and getattr(step, "direction", None) is None) else 0
     with torch.cuda.device(dev):
         rt.check(L.hgs_loss_head_forward(rt.current_stream(), C.byref(hp), planes[0:3].data_ptr(), planes[3].data_ptr(),
                                          planes[4:7].data_ptr(), vt.slot.data_ptr(), rt.ptr(endpoints), rt.ptr(smooth_idx),
@@ -687,6 +687,9 @@ class FusedStrandStep:
         self.magnet = None
         # the head's distance field (utils.head_sdf.HeadSDF) when the head-penetration term runs inside this iteration, else None
         self.head_sdf = None
+        # the direction term's topology table (hgs_runtime.fused.DirectionTable) when the 3-D direction term runs inside this
+        # iteration, else None
+        self.direction = None
         self.refresh()
 
     def inline_adam_possible(self):
@@ -694,10 +697,11 @@ class FusedStrandStep:
         rasterizer's (hgs_backward_multi_params; a strand model also needs the endpoint adjacency), a FusedAdam that holds
         exactly the in-lane tensors (higher SH coefficients would need a launch of their own) -- and not switched off.  Not with
         the magnet term: the endpoints' gradient then has a second contributor (autograd adds the two), so the update cannot
-        run in the gather's lanes and Adam's own launch returns.  The head-penetration term is such a contributor too."""
+        run in the gather's lanes and Adam's own launch returns.  The head-penetration term is such a contributor too, and so is
+        the 3-D direction term."""
         from hgs_runtime.fused import FusedAdam
         g = self.gaussians
-        return (self.magnet is None and self.head_sdf is None and self.fuse_param_backward
+        return (self.magnet is None and self.head_sdf is None and self.direction is None and self.fuse_param_backward
                 and isinstance(getattr(g, "optimizer", None), FusedAdam) and g._features_rest.numel() == 0
                 and getattr(self, "ep_segments", True) is not None
                 and bool(getattr(self.opt, "inline_adam", True)) and os.environ.get("HGS_INLINE_ADAM", "1") != "0"
@@ -743,6 +747,16 @@ class FusedStrandStep:
             self.head_sdf, self.head_margin = g.head_sdf, float(getattr(self.opt, "head_margin", 0.0))
             self.head_sdf.on(g._endpoints.device)      # (the field's device copy: made here, not inside a capture)
             self.head_scratch = HeadScratch(g._endpoints.shape[0], g._endpoints.device)
+        # the 3-D direction term inside the iteration (opt.lambda_direction > 0 and a volume on the model): its incidence table and
+        # scratch follow the topology
+        self.lambda_direction = float(getattr(self.opt, "lambda_direction", 0.0))
+        self.direction = self.direction_volume = self.direction_scratch = None
+        if self.lambda_direction > 0 and getattr(g, "direction_volume", None) is not None:
+            from hgs_runtime.fused import DirectionScratch, DirectionTable
+            self.direction_volume, self.direction_min_conf = g.direction_volume, float(getattr(self.opt, "direction_min_conf", 0.5))
+            self.direction_volume.on(g._endpoints.device)      # (the volume's device copy: made here, not inside a capture)
+            self.direction = DirectionTable.of(g)
+            self.direction_scratch = DirectionScratch(self.direction.S, self.direction.E, g._endpoints.device)
         # endpoint adjacency for the gather-mode backward (HgsStrandFusion.ep_segments / ep_pairs): an endpoint of a
         # chain touches <= 2 segments and <= 4 smoothness-pair roles; anything denser keeps the scatter (atomic) mode.
         # Remembered on the model for as long as both index tables are the same tensors (a topology event assigns new ones): the
@@ -784,6 +798,13 @@ class FusedStrandStep:
             hd = head_penalty(g._endpoints, self.head_sdf, self.head_margin, None, self.head_scratch)
             self.last["head"] = hd.detach()
             loss = loss + self.lambda_head * hd
+        if self.direction is not None:
+            # loss + lambda_direction * term, as loss_function_single_pass adds it: a further autograd node after the head term's
+            from hgs_runtime.fused import direction_loss
+            dr = direction_loss(g._endpoints, self.direction, self.direction_volume, self.direction_min_conf, None,
+                                self.direction_scratch)
+            self.last["direction"] = dr.detach()
+            loss = loss + self.lambda_direction * dr
         return loss, terms
 
     def backward(self, loss):
@@ -797,6 +818,8 @@ class FusedStrandStep:
             d["magnet"] = self.last["magnet"]
         if "head" in self.last:
             d["head"] = self.last["head"]
+        if "direction" in self.last:
+            d["direction"] = self.last["direction"]
         return d
 
     def update_densification_stats(self):
@@ -889,6 +912,7 @@ class FusedCloudStep(FusedStrandStep):
         self.smooth_pairs = None
         self.magnet = None          # (a Gaussian cloud has no strand ends)
         self.head_sdf = None        # (nor joints to keep out of the head: as with smoothness, Stage I has no such term)
+        self.direction = None       # (nor segments to align with the direction volume)
         self.head = head_params(self.views.H, self.views.W, self.opt, 0, 0, getattr(g, "min_val", 1e-7),
                                 self.views.has_float_mask)
 

@@ -204,6 +204,57 @@ def head_penetration_loss(gaussians: HairGaussianModel, sdf, margin):
     return pen.sum() / E
 
 
+def strand_direction_loss(gaussians: HairGaussianModel, volume, min_conf):
+    """Aligns the strand segments with the capture's 3-D hair lines (this package's own term, enabled by --lambda_direction, 0 by
+    default; the reference has none): the mean over ALL segments of sin^2 of the angle between the segment and the line that the
+    direction volume `volume` (a utils.direction_term.DirectionVolume) holds at the segment's midpoint, where the midpoint lies inside
+    the volume and the interpolated confidence reaches `min_conf`.  utils/direction_term.py states the arithmetic; this is the same
+    statement in torch ops, in the same order -- index arithmetic, where and gathers, no selection on the host, so it can be captured
+    and it runs on a CPU model; the sampled line, the confidence and the signs are formed on detached values (no gradient through the
+    lookup position), the endpoints receive theirs through the gathers' index_add; hgs_runtime.fused.direction_loss is the device op."""
+    p = gaussians._endpoints
+    pairs = gaussians.endpoint_pairs
+    S = pairs.shape[0]
+    if S == 0:
+        return p.sum() * 0.0
+    field = volume.on(p.device)
+    vol = field["vol"].to(p.dtype)
+    nx, ny, nz = volume.shape
+    a, b = p.index_select(0, pairs[:, 0]), p.index_select(0, pairs[:, 1])
+    u = b - a
+    uu = (u[:, 0] * u[:, 0] + u[:, 1] * u[:, 1]) + u[:, 2] * u[:, 2]
+    with torch.no_grad():
+        ud = u.detach()
+        m = (a.detach() + b.detach()) * 0.5
+        t = (m - field["origin"].to(p.dtype)) * field["inv_h"].to(p.dtype)
+        ok = (torch.isfinite(t) & (t >= 0) & (t < field["top"].to(p.dtype))).all(dim=1)
+        t = torch.where(ok[:, None], t, torch.zeros_like(t))                 # (rows out of range: any valid address)
+        fl = torch.floor(t)
+        f = t - fl
+        i = fl.long()
+        g = (1.0 - f, f)
+        w = torch.zeros_like(uu)
+        v = [torch.zeros_like(uu) for _ in range(3)]
+        for z in (0, 1):
+            for y in (0, 1):
+                for x in (0, 1):
+                    tw = (g[x][:, 0] * g[y][:, 1]) * g[z][:, 2]
+                    c = vol[((i[:, 2] + z) * ny + (i[:, 1] + y)) * nx + (i[:, 0] + x)]
+                    q = tw * c[:, 3]
+                    w = w + q
+                    q = torch.where((c[:, 0] * ud[:, 0] + c[:, 1] * ud[:, 1]) + c[:, 2] * ud[:, 2] < 0, -q, q)
+                    v = [v[j] + q * c[:, j] for j in range(3)]
+        nn = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]
+        uud = uu.detach()
+        active = ok & (w >= min_conf) & torch.isfinite(nn) & (nn > 0) & torch.isfinite(uud) & (uud > 0)
+        ln = torch.sqrt(torch.where(active, nn, torch.ones_like(nn)))
+        fd = [torch.where(active, v[j] / ln, torch.zeros_like(ln)) for j in range(3)]
+    cu = (u[:, 0] * fd[0] + u[:, 1] * fd[1]) + u[:, 2] * fd[2]
+    k = cu / torch.where(active, uu, torch.ones_like(uu))
+    term = torch.where(active, 1.0 - cu * k, torch.zeros_like(cu))
+    return term.sum() / S
+
+
 _BLACK = {}
 _BG_HOST = {}
 
@@ -316,6 +367,9 @@ def loss_function_single_pass(gaussians, viewpoint_cam, args, bg, black_backgrou
         if getattr(args, "lambda_head", 0.0) > 0 and getattr(gaussians, "head_sdf", None) is not None:
             terms["head"] = head_penetration_loss(gaussians, gaussians.head_sdf, getattr(args, "head_margin", 0.0))
             loss = loss + args.lambda_head * terms["head"]
+        if getattr(args, "lambda_direction", 0.0) > 0 and getattr(gaussians, "direction_volume", None) is not None:
+            terms["direction"] = strand_direction_loss(gaussians, gaussians.direction_volume, getattr(args, "direction_min_conf", 0.5))
+            loss = loss + args.lambda_direction * terms["direction"]
     return loss, terms, pkg
 
 
@@ -345,4 +399,7 @@ def loss_function(gaussians, image, viewpoint_cam, args):
         if getattr(args, "lambda_head", 0.0) > 0 and getattr(gaussians, "head_sdf", None) is not None:
             terms["head"] = head_penetration_loss(gaussians, gaussians.head_sdf, getattr(args, "head_margin", 0.0))
             loss = loss + args.lambda_head * terms["head"]
+        if getattr(args, "lambda_direction", 0.0) > 0 and getattr(gaussians, "direction_volume", None) is not None:
+            terms["direction"] = strand_direction_loss(gaussians, gaussians.direction_volume, getattr(args, "direction_min_conf", 0.5))
+            loss = loss + args.lambda_direction * terms["direction"]
     return loss, terms

@@ -16,7 +16,10 @@ def main(argv=None):
     Resumes from the newest <model dir>/point_cloud/iteration_*/point_cloud.ply (Gaussian cloud = Stage I, strand model =
     Stage III) or starts Stage I from the sparse COLMAP points; saves every save_frequency iterations and at the end.
     --lambda_head L (this package's own, off by default) adds the head-penetration term to a strand model's loss; it needs
-    <scene>/head_sdf.npz, which head_sdf.py builds (utils/head_sdf.py)."""
+    <scene>/head_sdf.npz, which head_sdf.py builds (utils/head_sdf.py).
+    --lambda_direction L --direction_field PATH [--direction_min_conf 0.5] (this package's own, off by default) adds the 3-D direction
+    term to a strand model's loss: every segment is aligned with the hair line that the capture's direction volume, the .npz that
+    trace_strands.py --field PATH [--fill N] writes, holds at its midpoint (utils/direction_term.py)."""
     from argparse import ArgumentParser
     from arguments import GeneralParams, ModelParams, OptimizationParams
     from scene import Scene
@@ -36,6 +39,18 @@ def main(argv=None):
             head_sdf = load_sdf(path)
         except ValueError as e:
             raise SystemExit(f"train.py: {e}") from None
+    direction_volume = None
+    if float(args.lambda_direction) > 0:
+        # the 3-D direction term needs the capture's direction volume: looked for before anything is loaded or written
+        from utils.direction_term import DirectionVolume
+        path = os.path.abspath(args.direction_field) if args.direction_field else ""
+        if not path or not os.path.isfile(path):
+            raise SystemExit(f"train.py: --lambda_direction {args.lambda_direction} needs --direction_field PATH, the direction volume "
+                             f"that trace_strands.py --field PATH writes ({path or 'no path given'}: no such file)")
+        try:
+            direction_volume = DirectionVolume.load(path)
+        except ValueError as e:
+            raise SystemExit(f"train.py: {e}; trace_strands.py --field PATH writes a direction volume") from None
     # view-parallel run (python -m torch.distributed.run ... train.py): one process per GPU, initialised before anything
     # touches the GPU; every rank seeds identically (replicated topology operators draw the same random numbers), rank 0
     # alone writes to the model directory
@@ -68,6 +83,12 @@ def main(argv=None):
     g = scene.gaussians
     if head_sdf is not None:
         g.head_sdf = head_sdf    # rides on the model: loss/losses.py and hgs_runtime/strand_step.py read gaussians.head_sdf
+    if direction_volume is not None:
+        from scene.hair_gaussian_model import HairGaussianModel
+        if isinstance(g, HairGaussianModel):
+            g.direction_volume = direction_volume    # rides on the model like head_sdf: the same two readers
+        elif rank == 0:
+            print("train.py: --lambda_direction applies to strand models only; this Stage-I run goes on without the term")
     g.training_setup(opt)
     cams = scene.getCameras()
     vp = ViewParallel()

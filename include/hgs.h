@@ -956,6 +956,29 @@ int hgs_head_penalty_forward(void* stream, int E, const float* points, const flo
                              float oz, float inv_h, float margin, float* g, float* pen, float* dist, double* partials, float* out);
 int hgs_head_penalty_backward(void* stream, int E, const float* g, const float* upstream, float* d_points);
 
+/* hgs_direction_loss_* (csrc/hgs_direction.hip) <-> the 3-D direction term of a strand model (utils/direction_term.py states the
+ *   contract and has the numpy path; train.py --lambda_direction; the reference has nothing of the kind).  Added under ABI 15.
+ * hgs_direction_loss_forward: points [E][3] float32; pairs [S][2] int64, every entry in [0, E): the caller's duty (the Python binding
+ *   checks it when it builds the incidence table).  vol [nz][ny][nx][4] float32 = (dir.x, dir.y, dir.z, conf) per node, 16-byte
+ *   aligned; origin and 1/h rounded to float32.  Per segment, float32, one rounding per operation: a, b its endpoints, u = b - a,
+ *   m = (a + b) * 0.5, t = (m - origin) * inv_h; in range iff 0 <= t < n - 1 on every axis (a NaN is not; the test precedes every
+ *   load); the eight corners with z outermost, then y, then x: tw = (gx gy) gz, q = tw conf, w += q, q = -q where dot(dir, u) < 0,
+ *   v += q dir; active iff in range, w >= min_conf and dot(v, v), dot(u, u) finite and > 0; fd = v / sqrt(dot(v, v)), cu = dot(u, fd),
+ *   k = cu / dot(u, u); term = 1 - cu k, gs = (-2 k)(fd - k u); both 0 where inactive.  gs [S][3] (scratch the backward reads), term
+ *   [S] and w [S] (both nullable), partials: 2 * hgs_direction_loss_num_blocks(S) doubles of scratch, out [2]: [0] = float(sum of
+ *   term in float64 / S), 0 for S = 0; [1] = the number of active segments, int32 bits.  Two launches, bitwise reproducible, no
+ *   atomics.  2 <= n <= 1024 an axis, at most 2^26 nodes, 0 <= S <= 2^28.
+ * hgs_direction_loss_backward: the incidence table of the endpoints as CSR: offsets [E + 1] int32, entries [2 S] int32 = 2 s + side
+ *   for every pairs[s][side] == e, ascending within an endpoint's run (trusted).  d_points [E][3] = acc * (upstream[0] / float(S)),
+ *   acc the float32 sum over the run, in order, of +gs[s] (side 1) or -gs[s] (side 0); upstream in device memory; every endpoint is
+ *   written (0 for one that no segment uses, and for S = 0).  One launch, no atomics. */
+int hgs_direction_loss_num_blocks(int S);
+int hgs_direction_loss_forward(void* stream, int S, const float* points, const long long* pairs, const float* vol, int nx, int ny, int nz,
+                               float ox, float oy, float oz, float inv_h, float min_conf, float* gs, float* term, float* w,
+                               double* partials, float* out);
+int hgs_direction_loss_backward(void* stream, int E, int S, const int* offsets, const int* entries, const float* gs,
+                                const float* upstream, float* d_points);
+
 /* hgs_strand_collide (csrc/hgs_collide.hip) <-> the push-out of exported strands (scene/strand_collide.py states the contract and has
  *   the numpy path; export_strands.py --resolve_head; the reference has nothing of the kind): every strand is walked from its root, a
  *   joint inside the head (in range and d < margin) is pushed along the field's gradient to margin + skin, and every joint behind a
