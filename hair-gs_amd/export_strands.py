@@ -7,6 +7,7 @@ merge.py that the reference leaves to scripts/convert_output.py (MeshLab PLYs of
                            [--resolve_head [--head_margin 0] [--collide_iters 8] [--head_sdf PATH]]
                            [--attach_roots [--attach_margin 0] [--attach_step S] [--attach_max_steps 256] [--attach_pull 1] [--attach_descent 0.25]
                             [--attach_max_distance D] [--attach_field PATH] [--attach_min_conf 0.5] [--attach_scalp_distance D] [--drop_unattached]]
+                           [--smooth_strands [--smooth_iters 10] [--smooth_lambda 0.5] [--smooth_mu -0.53] [--smooth_max_move D]]
 A model directory is read at its newest point_cloud/iteration_N (utils/system.py model_ply, as eval.py reads it); the SH degree is read off the file.  Every
 strand is resampled by arc length to --points points (0: its joints as they are) with per-point colour, opacity and width
 (scene/strand_export.py: the contract; --device cuda = the HIP kernels on the model's device tensors, cpu = the numpy path), strands
@@ -43,7 +44,18 @@ to M points again.  A strand already on the head, one farther than --attach_max_
 their bits (--drop_unattached drops the failed ones); with --attach_scalp_distance D a strand that landed farther than D from every
 strand root -- on the face or the neck -- is restored too.  The strands attached, already rooted, failed by reason and dropped, the
 joints added, the largest and mean root gap before and the largest |d - margin| of the landed roots are printed.  Without the flag
-the strands are written as they are."""
+the strands are written as they are.
+--smooth_strands low-passes every strand (scene/strand_smooth.py: the contract): the joints are trained Gaussian endpoints, which jitter
+from segment to segment, and a renderer that takes its tangents from neighbouring points shades that jitter as frizz.  After the
+resampling and --attach_roots (the kink where the marched joints meet the strand's own is smoothed with the landed root pinned), before
+--interpolate (guides are smoothed before they are blended) and --resolve_head (a joint the filter pulled into the head is pushed out
+again), --smooth_iters (1 to 256) times a sweep that moves every inner joint by --smooth_lambda towards the mean of its neighbours,
+weighted by the original segment lengths, is followed by one with --smooth_mu (negative, below -lambda: Taubin's filter, which does
+not shrink the strand; 0: plain Laplacian smoothing, which does); with --smooth_max_move D no joint ends farther than D from where it
+was.  Roots, tips and attributes keep their bits, strands of fewer than 3 or more than 1024 joints or with a coordinate that is not
+finite are left alone and counted, and the spacing is not made uniform again.  The strands smoothed and left alone, the joints held at
+D, the largest and mean displacement, the mean turning angle per joint before and after and the strands' length ratios are printed.
+Without the flag the strands are written as they are."""
 import os
 import sys
 
@@ -172,6 +184,20 @@ def attached(args, path, model, strands):
     return out
 
 
+def smoothed(args, strands):
+    """--smooth_strands: the strands low-passed (scene/strand_smooth.py), and what that did."""
+    from scene.strand_smooth import smooth_strands
+    out, rep = smooth_strands(strands, iters=args.smooth_iters, lam=args.smooth_lambda, mu=args.smooth_mu, max_move=args.smooth_max_move,
+                              device=None if args.device == "cpu" else args.device)
+    print(f"Smoothed strands ({args.smooth_iters} x lambda {args.smooth_lambda:g} | mu {args.smooth_mu:g}): {rep['smoothed']} of {rep['strands']} "
+          f"strands smoothed, left alone: {rep['short']} short, {rep['long']} long, {rep['nonfinite']} not finite; {rep['joints']} joints, "
+          + (f"{rep['clamped']} held at {args.smooth_max_move:g}, " if args.smooth_max_move is not None else "")
+          + f"largest displacement {rep['largest_displacement']:.4g}, mean {rep['mean_displacement']:.4g}; mean turning angle per joint "
+          f"{rep['turning_before']:.4g} -> {rep['turning_after']:.4g} degrees; length after / before: {rep['length_ratio_min']:.4f} to "
+          f"{rep['length_ratio_max']:.4f}, mean {rep['length_ratio_mean']:.4f}")
+    return out
+
+
 def main(argv=None):
     parser = ArgumentParser(description="Export the strands of a trained model as hair assets")
     parser.add_argument("--model_path", "-m", required=True, help="a strand model PLY, or a model directory")
@@ -205,8 +231,19 @@ def main(argv=None):
     parser.add_argument("--attach_min_conf", type=float, default=0.5, help="with --attach_roots: least aligned mass the volume must have at a point to steer")
     parser.add_argument("--attach_scalp_distance", type=float, default=None, help="with --attach_roots: a landed root farther than this from every strand root is off the scalp; its strand is restored")
     parser.add_argument("--drop_unattached", action="store_true", help="with --attach_roots: drop the strands whose march failed (default: write them unchanged)")
+    parser.add_argument("--smooth_strands", action="store_true", help="low-pass every strand (Taubin's lambda|mu filter, both ends pinned)")
+    parser.add_argument("--smooth_iters", type=int, default=10, help="with --smooth_strands: lambda|mu sweep pairs (1 to 256)")
+    parser.add_argument("--smooth_lambda", type=float, default=0.5, help="with --smooth_strands: the smoothing sweep's factor (above 0, at most 1)")
+    parser.add_argument("--smooth_mu", type=float, default=-0.53, help="with --smooth_strands: the inflating sweep's factor (-1 to below -lambda; 0: none, the strands shrink)")
+    parser.add_argument("--smooth_max_move", type=float, default=None, help="with --smooth_strands: no joint ends farther than this from where it was")
     args = parser.parse_args(argv)
     field = None
+    if args.smooth_strands:
+        from scene.strand_smooth import check_parameters as check_smooth
+        try:
+            check_smooth(args.smooth_iters, args.smooth_lambda, args.smooth_mu, args.smooth_max_move)
+        except ValueError as e:
+            parser.exit(2, f"export_strands.py: --smooth_strands: {e}\n")
     if args.attach_roots:
         from scene.strand_attach import MAX_STEPS as ATTACH_MAX_STEPS
         for flag, value, good, words in (
@@ -254,6 +291,8 @@ def main(argv=None):
           + (f" ({args.points} per strand)" if args.points else " (the joints)"))
     if args.attach_roots:
         result = attached(args, field, model, result)
+    if args.smooth_strands:
+        result = smoothed(args, result)
     if args.interpolate:
         result = interpolated(args, model, result)
     if args.resolve_head:

@@ -1042,6 +1042,29 @@ int hgs_strand_rejoin(void* stream, int K, const long long* offsets, long long P
                       const double* ext, int ext_rows, const int* count, const int* reason, int M, const long long* out_offsets,
                       long long n_out, float* out_points, float* out_attrs);
 
+/* hgs_strand_smooth (csrc/hgs_strand_smooth.hip) <-> exported strands smoothed without shrinking them (scene/strand_smooth.py states
+ *   the contract and has the numpy path; export_strands.py --smooth_strands; the reference has nothing of the kind).  Added under
+ *   ABI 15.  Taubin's lambda|mu low-pass over every strand's polyline, both end joints pinned, weights from the original segment
+ *   lengths.  Strands as for hgs_strand_collide: K strands over points [P][3] float32 through offsets [K + 1] int64 (the caller's
+ *   duty; a range that does not lie inside the P points counts as a strand without joints).  Per strand with joints p_0 .. p_{n-1},
+ *   float64, one rounding per operation, dot(u, v) = (u0*v0 + u1*v1) + u2*v2:
+ *     n < 3: status 1 (short).  n > 1024: status 2 (long).  Any coordinate not finite: status 3.  The strand is copied.
+ *     Otherwise status 0:  l_i = sqrt(dot(e_i, e_i)) for e_i = p_{i+1} - p_i;  for inner j = 1 .. n-2: s_j = l_{j-1} + l_j, a_j =
+ *     l_j / s_j and b_j = l_{j-1} / s_j where s_j > 0, else both 0.5.  A sweep with factor f (Jacobi: sweep t+1 reads sweep t only):
+ *     m = a_j*x_{j-1}[c] + b_j*x_{j+1}[c]; x'_j[c] = x_j[c] + f*(m - x_j[c]) for every inner j and coordinate c; x_0 and x_{n-1} stay.
+ *     iters (1 to 256) times: a sweep with lam, then, unless mu == 0, a sweep with mu.  With has_max_move != 0, for every inner j:
+ *     u = x_j - p_j, du = sqrt(dot(u, u)); if du > max_move: x_j = p_j + (max_move / du)*u and clamped[s] += 1.  out_j = float32(x_j)
+ *     for the inner joints; the two end joints get their input bits.
+ *   0 < lam <= 1; mu == 0 or -1 <= mu < -lam; |(1 - 2 lam)(1 - 2 mu)| <= 1; max_move finite and > 0 where has_max_move != 0 (it is
+ *   not looked at otherwise).  max_joints (0 to 1024): the number of joints of the launch's longest strand with 3 <= n <= 1024, which
+ *   the caller reads off the offsets (0 where there is none); it sizes the dynamic LDS -- one wavefront per strand keeps the strand in
+ *   five float64 rows of max_joints entries, 4, 2 or 1 wavefronts a workgroup, whichever is the most that fits 64 KB -- and a strand
+ *   longer than it is treated as long, never written past its slice.  out_points [P][3] float32 must not alias points; status,
+ *   clamped [K] int32.  No atomics, bitwise reproducible.  Bad sizes, iters or parameters and, for K > 0, null or aliased pointers
+ *   return 1 before anything is launched; K == 0 returns 0. */
+int hgs_strand_smooth(void* stream, int K, const long long* offsets, long long P, const float* points, int max_joints, int iters,
+                      double lam, double mu, int has_max_move, double max_move, float* out_points, int* status, int* clamped);
+
 /* Strands traced from the scalp through the lifted hair directions (csrc/hgs_trace.hip; utils/trace.py states the contract and has
  *   the numpy paths).  All float64, one rounding per operation.  Every argument is checked before a pointer is touched.  The grid:
  *   node (ix, iy, iz) lies at origin + index * h, 2 <= n <= 1024 an axis, at most 2^26 nodes in all.
