@@ -8,6 +8,7 @@ merge.py that the reference leaves to scripts/convert_output.py (MeshLab PLYs of
                            [--attach_roots [--attach_margin 0] [--attach_step S] [--attach_max_steps 256] [--attach_pull 1] [--attach_descent 0.25]
                             [--attach_max_distance D] [--attach_field PATH] [--attach_min_conf 0.5] [--attach_scalp_distance D] [--drop_unattached]]
                            [--smooth_strands [--smooth_iters 10] [--smooth_lambda 0.5] [--smooth_mu -0.53] [--smooth_max_move D]]
+                           [--select_guides K [--select_samples 16] [--select_iters 10]]
 A model directory is read at its newest point_cloud/iteration_N (utils/system.py model_ply, as eval.py reads it); the SH degree is read off the file.  Every
 strand is resampled by arc length to --points points (0: its joints as they are) with per-point colour, opacity and width
 (scene/strand_export.py: the contract; --device cuda = the HIP kernels on the model's device tensors, cpu = the numpy path), strands
@@ -55,7 +56,17 @@ not shrink the strand; 0: plain Laplacian smoothing, which does); with --smooth_
 was.  Roots, tips and attributes keep their bits, strands of fewer than 3 or more than 1024 joints or with a coordinate that is not
 finite are left alone and counted, and the spacing is not made uniform again.  The strands smoothed and left alone, the joints held at
 D, the largest and mean displacement, the mean turning angle per joint before and after and the strands' length ratios are printed.
-Without the flag the strands are written as they are."""
+Without the flag the strands are written as they are.
+--select_guides K picks K guide strands from the strands that are written (scene/strand_guides.py: the contract): what a simulation of
+the groom wants -- a few representative strands, and for every written strand the guide it follows.  It runs last, after --interpolate
+and --resolve_head and just in front of the writers, on exactly the strands that are written, and needs a fixed number of points per
+strand (--points M > 0).  Lloyd's k-means over --select_samples (2 to 64) joints taken evenly along every strand, seeded by index, at
+most --select_iters (1 to 256) assignments; every cluster's most central member is its guide.  The main outputs are written as without
+the flag, byte for byte; for every --format the guide strands go to the same path with _guides in front of the extension, and
+<out>_guide_binding.npz holds guide_strand (the guide's index among the written strands), strand_guide (every written strand's guide,
+-1 for a strand with a coordinate that is not finite), strand_distance (the RMS joint distance to the cluster's centre), cluster_size,
+k, samples, iterations and converged.  The guides made, the empty clusters, the iterations, the cluster sizes, the distances and the
+total squared distance after the first and the last assignment are printed.  --guides belongs to --interpolate and is another thing."""
 import os
 import sys
 
@@ -198,6 +209,36 @@ def smoothed(args, strands):
     return out
 
 
+def selected(args, strands):
+    """--select_guides: (guide strands, binding) of the strands that are written (scene/strand_guides.py), and what that did."""
+    from scene.strand_guides import select_guides
+    guides, binding, rep = select_guides(strands, args.select_guides, samples=args.select_samples, iters=args.select_iters,
+                                         device=None if args.device == "cpu" else args.device)
+    print(f"Selected guides (k {args.select_guides}, {args.select_samples} samples, at most {args.select_iters} iterations): {guides.n_strands} "
+          f"guides from {rep['eligible']} of {rep['strands']} strands ({rep['nonfinite']} not finite), {rep['clusters_empty']} of "
+          f"{rep['clusters_made']} clusters empty; {rep['iterations']} iterations, " + ("converged" if rep["converged"] else "not converged")
+          + f"; cluster size {rep['size_min']} to {rep['size_max']}, mean {rep['size_mean']:.4g}; RMS joint distance to the centre: mean "
+          f"{rep['distance_mean']:.4g}, largest {rep['distance_max']:.4g}; total squared distance {rep['total_first']:.6g} -> {rep['total_last']:.6g}")
+    binding = dict(binding, k=np.int64(args.select_guides), samples=np.int64(args.select_samples), iterations=np.int64(rep["iterations"]),
+                   converged=np.bool_(rep["converged"]))
+    return guides, binding
+
+
+def write_formats(paths, formats, strands, colour):
+    """One file per format of `formats` at paths[format] (data/strand_files.py)."""
+    from data import strand_files as F
+    for f in formats:
+        if f == "hair":
+            F.write_strands_cy(paths[f], strands)
+        elif f == "usc":
+            F.write_strands_usc(paths[f], strands)
+        elif f == "npz":
+            F.write_strands_npz(paths[f], strands)
+        else:
+            F.write_strands_ply(paths[f], strands, faces=(f == "ply_faces"), colour=colour)
+        print(f"Saved {f}: {paths[f]}")
+
+
 def main(argv=None):
     parser = ArgumentParser(description="Export the strands of a trained model as hair assets")
     parser.add_argument("--model_path", "-m", required=True, help="a strand model PLY, or a model directory")
@@ -236,7 +277,19 @@ def main(argv=None):
     parser.add_argument("--smooth_lambda", type=float, default=0.5, help="with --smooth_strands: the smoothing sweep's factor (above 0, at most 1)")
     parser.add_argument("--smooth_mu", type=float, default=-0.53, help="with --smooth_strands: the inflating sweep's factor (-1 to below -lambda; 0: none, the strands shrink)")
     parser.add_argument("--smooth_max_move", type=float, default=None, help="with --smooth_strands: no joint ends farther than this from where it was")
+    parser.add_argument("--select_guides", type=int, default=None, metavar="K", help="pick K guide strands from the written strands by k-means, with a binding (1 to 65536)")
+    parser.add_argument("--select_samples", type=int, default=16, help="with --select_guides: joints compared per strand (2 to 64)")
+    parser.add_argument("--select_iters", type=int, default=10, help="with --select_guides: assignments at most (1 to 256)")
     args = parser.parse_args(argv)
+    if args.select_guides is not None:
+        from scene.strand_guides import check_parameters as check_select
+        try:
+            check_select(args.select_guides, args.select_samples, args.select_iters)
+        except ValueError as e:
+            parser.exit(2, f"export_strands.py: --select_guides: {e}\n")
+        if args.points <= 0:
+            parser.exit(2, "export_strands.py: --select_guides compares strands joint by joint and needs a fixed number of points per strand: "
+                           "--points M > 0 is needed (--points 0, the joints themselves, cannot be combined with it)\n")
     field = None
     if args.smooth_strands:
         from scene.strand_smooth import check_parameters as check_smooth
@@ -279,7 +332,6 @@ def main(argv=None):
         parser.exit(2, "export_strands.py: --interpolate blends strands point by point and needs a fixed number of points per strand: "
                        "--points 0 (the joints themselves) cannot be combined with it\n")
     formats = list(dict.fromkeys(args.format or ["hair"]))
-    from data import strand_files as F
     from scene.strand_export import resample_strands
     from utils.system import model_ply
     ply = model_ply(args.model_path)
@@ -299,16 +351,21 @@ def main(argv=None):
         result = resolved(args, field, result)
     paths = output_paths(args.output, formats)
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
-    for f in formats:
-        if f == "hair":
-            F.write_strands_cy(paths[f], result)
-        elif f == "usc":
-            F.write_strands_usc(paths[f], result)
-        elif f == "npz":
-            F.write_strands_npz(paths[f], result)
-        else:
-            F.write_strands_ply(paths[f], result, faces=(f == "ply_faces"), colour=args.colour)
-        print(f"Saved {f}: {paths[f]}")
+    picked = None
+    if args.select_guides is not None:
+        try:
+            picked = selected(args, result)
+        except ValueError as e:
+            parser.exit(2, f"export_strands.py: --select_guides: {e}\n")
+    write_formats(paths, formats, result, args.colour)
+    if picked is not None:
+        guides, binding = picked
+        guide_paths = {f: "_guides".join(os.path.splitext(p)) for f, p in paths.items()}
+        write_formats(guide_paths, formats, guides, args.colour)
+        paths = dict(paths, **{f + "_guides": p for f, p in guide_paths.items()})
+        paths["guide_binding"] = output_paths(args.output, ["npz"])["npz"][:-len(".npz")] + "_guide_binding.npz"
+        np.savez(paths["guide_binding"], **binding)
+        print(f"Saved guide binding: {paths['guide_binding']}")
     return result, paths
 
 

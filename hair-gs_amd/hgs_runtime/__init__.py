@@ -120,6 +120,9 @@ SIGNATURES = {
                              vp]),
     "hgs_strand_rejoin": (ci, [vp, ci, vp, C.c_longlong, vp, vp, ci, vp, ci, vp, vp, ci, vp, C.c_longlong, vp, vp]),
     "hgs_strand_smooth": (ci, [vp, ci, vp, C.c_longlong, vp, ci, ci, C.c_double, C.c_double, ci, C.c_double, vp, vp, vp]),
+    "hgs_guides_assign": (ci, [vp, ci, ci, ci, C.c_longlong, vp, vp, ci, vp, vp, vp, vp, vp]),
+    "hgs_guides_update": (ci, [vp, ci, ci, ci, C.c_longlong, vp, ci, vp, C.c_longlong, vp, vp, vp]),
+    "hgs_guides_pick": (ci, [vp, ci, ci, vp, C.c_longlong, vp, vp, vp]),
     "hgs_field_splat": (ci, [vp, ci, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, C.c_double, vp, vp]),
     "hgs_field_solve": (ci, [vp, ci, ci, ci, vp, vp, vp]),
     "hgs_strand_trace": (ci, [vp, ci, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, C.c_double, ci,

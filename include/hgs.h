@@ -1065,6 +1065,27 @@ int hgs_strand_rejoin(void* stream, int K, const long long* offsets, long long P
 int hgs_strand_smooth(void* stream, int K, const long long* offsets, long long P, const float* points, int max_joints, int iters,
                       double lam, double mu, int has_max_move, double max_move, float* out_points, int* status, int* clamped);
 
+/* hgs_guides_assign / hgs_guides_update / hgs_guides_pick (csrc/hgs_guides.hip) <-> guide strands picked from an exported groom by
+ *   Lloyd's k-means (scene/strand_guides.py states the contract and has the numpy path; export_strands.py --select_guides).  N strands
+ *   of M >= 2 points each, points float32 [n_points][3] with N*M <= n_points; strand i's feature is its S sampled points
+ *   j_s = (s*(M-1)) / (S-1), 2 <= S <= min(64, M), as doubles; centroids float64 [K][S][3], 1 <= K <= 65536.  All arithmetic is float64,
+ *   one rounding per operation in the order written.  Every argument is checked before anything is launched; N == 0 returns 0.
+ * hgs_guides_assign: status int32 [N] (0: the strand takes part; anything else: label -1, dist2 +inf).  d2(i, k) is accumulated from
+ *   0.0 over s in order, acc = acc + ((dx*dx + dy*dy) + dz*dz), d = feature - centroid; label [N] int32 = the k smallest by (d2, k),
+ *   dist2 [N] float64 its d2.  prev_label (may be NULL): changed [1] int32 is ADDED the number of strands whose label differs from
+ *   prev_label's (an integer atomic; the caller zeroes it).  label must not alias prev_label or status.  Bitwise reproducible.
+ * hgs_guides_update: order int64 [n_order] lists the strands that have a label, sorted by label and, within one, ascending (a stable
+ *   sort), start int64 [K + 1] the clusters' ranges in it.  For every cluster with members each of its 3S coordinates becomes the sum
+ *   of the members' coordinates, added from 0.0 in list order, divided by the member count as a double; an empty cluster keeps its
+ *   centroid.  count [K] int32 = the members.  Entries of order outside [0, N) and ranges outside [0, n_order] are skipped.
+ * hgs_guides_pick: guide [K] int64 = the member of cluster k smallest by (dist2, i); -1 for an empty cluster. */
+int hgs_guides_assign(void* stream, int N, int M, int S, long long n_points, const float* points, const int* status, int K,
+                      const double* centroids, const int* prev_label, int* label, double* dist2, int* changed);
+int hgs_guides_update(void* stream, int N, int M, int S, long long n_points, const float* points, int K, const long long* order,
+                      long long n_order, const long long* start, double* centroids, int* count);
+int hgs_guides_pick(void* stream, int N, int K, const long long* order, long long n_order, const long long* start, const double* dist2,
+                    long long* guide);
+
 /* Strands traced from the scalp through the lifted hair directions (csrc/hgs_trace.hip; utils/trace.py states the contract and has
  *   the numpy paths).  All float64, one rounding per operation.  Every argument is checked before a pointer is touched.  The grid:
  *   node (ix, iy, iz) lies at origin + index * h, 2 <= n <= 1024 an axis, at most 2^26 nodes in all.
