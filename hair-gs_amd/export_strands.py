@@ -9,6 +9,7 @@ merge.py that the reference leaves to scripts/convert_output.py (MeshLab PLYs of
                             [--attach_max_distance D] [--attach_field PATH] [--attach_min_conf 0.5] [--attach_scalp_distance D] [--drop_unattached]]
                            [--smooth_strands [--smooth_iters 10] [--smooth_lambda 0.5] [--smooth_mu -0.53] [--smooth_max_move D]]
                            [--select_guides K [--select_samples 16] [--select_iters 10]]
+                           [--simplify TOL]
 A model directory is read at its newest point_cloud/iteration_N (utils/system.py model_ply, as eval.py reads it); the SH degree is read off the file.  Every
 strand is resampled by arc length to --points points (0: its joints as they are) with per-point colour, opacity and width
 (scene/strand_export.py: the contract; --device cuda = the HIP kernels on the model's device tensors, cpu = the numpy path), strands
@@ -66,7 +67,19 @@ the flag, byte for byte; for every --format the guide strands go to the same pat
 <out>_guide_binding.npz holds guide_strand (the guide's index among the written strands), strand_guide (every written strand's guide,
 -1 for a strand with a coordinate that is not finite), strand_distance (the RMS joint distance to the cluster's centre), cluster_size,
 k, samples, iterations and converged.  The guides made, the empty clusters, the iterations, the cluster sizes, the distances and the
-total squared distance after the first and the last assignment are printed.  --guides belongs to --interpolate and is another thing."""
+total squared distance after the first and the last assignment are printed.  --guides belongs to --interpolate and is another thing.
+--simplify TOL drops every joint that lies within TOL (scene units) of the chord that replaces it (scene/strand_simplify.py: the
+contract): the chain up to here keeps a strand's point count or multiplies it, --points is one number for all strands, and after
+--smooth_strands most joints lie on their neighbours' chord to well under a hair's width, while .hair, .data and the PLYs are ragged by
+design.  It is Douglas-Peucker's rule with the distance to the segment, so a curl that turns back over its chord is not flattened; it
+runs last, directly in front of the writers, on exactly the strands that are written -- after --interpolate and --resolve_head, and
+after --select_guides has chosen (the k-means needs the uniform strands): the guide files then hold the simplified strands at
+guide_strand, and <out>_guide_binding.npz is what it is without the flag.  Kept joints keep the bits of their points and attributes,
+roots and tips are always kept, strands of fewer than 3 or more than 1024 joints or with a coordinate that is not finite are left
+alone and counted, and attributes are not looked at: the line `Simplified strands (tol ...): ...` says how many joints are left, how
+many a strand keeps, the rounds taken, the largest deviation of a dropped joint and, per attribute, how far a dropped joint's value
+was from linear between the kept joints around it.  It works with --points 0 too.  Without the flag the strands are written as they
+are."""
 import os
 import sys
 
@@ -224,6 +237,18 @@ def selected(args, strands):
     return guides, binding
 
 
+def simplified(args, strands):
+    """--simplify: the strands with the joints within TOL of their chord dropped (scene/strand_simplify.py), and what that did."""
+    from scene.strand_simplify import simplify_strands
+    out, rep = simplify_strands(strands, args.simplify, device=None if args.device == "cpu" else args.device)
+    print(f"Simplified strands (tol {args.simplify:g}): {rep['joints_after']} of {rep['joints_before']} joints kept ({rep['ratio']:.4f}); "
+          f"{rep['ok']} of {rep['strands']} strands simplified, left alone: {rep['short']} short, {rep['long']} long, {rep['nonfinite']} not "
+          f"finite; joints kept per strand {rep['kept_min']} to {rep['kept_max']}, mean {rep['kept_mean']:.4g}; at most {rep['rounds_max']} "
+          f"rounds; largest deviation of a dropped joint {rep['largest_deviation']:.4g}; largest attribute deviation from linear: "
+          + ", ".join(f"{v:.3g}" for v in rep["attr_deviation"]))
+    return out
+
+
 def write_formats(paths, formats, strands, colour):
     """One file per format of `formats` at paths[format] (data/strand_files.py)."""
     from data import strand_files as F
@@ -280,6 +305,7 @@ def main(argv=None):
     parser.add_argument("--select_guides", type=int, default=None, metavar="K", help="pick K guide strands from the written strands by k-means, with a binding (1 to 65536)")
     parser.add_argument("--select_samples", type=int, default=16, help="with --select_guides: joints compared per strand (2 to 64)")
     parser.add_argument("--select_iters", type=int, default=10, help="with --select_guides: assignments at most (1 to 256)")
+    parser.add_argument("--simplify", type=float, default=None, metavar="TOL", help="drop every joint within TOL (scene units) of the chord that replaces it; runs last")
     args = parser.parse_args(argv)
     if args.select_guides is not None:
         from scene.strand_guides import check_parameters as check_select
@@ -290,6 +316,12 @@ def main(argv=None):
         if args.points <= 0:
             parser.exit(2, "export_strands.py: --select_guides compares strands joint by joint and needs a fixed number of points per strand: "
                            "--points M > 0 is needed (--points 0, the joints themselves, cannot be combined with it)\n")
+    if args.simplify is not None:
+        from scene.strand_simplify import check_parameters as check_simplify
+        try:
+            check_simplify(args.simplify)
+        except ValueError as e:
+            parser.exit(2, f"export_strands.py: --simplify: {e}\n")
     field = None
     if args.smooth_strands:
         from scene.strand_smooth import check_parameters as check_smooth
@@ -357,9 +389,14 @@ def main(argv=None):
             picked = selected(args, result)
         except ValueError as e:
             parser.exit(2, f"export_strands.py: --select_guides: {e}\n")
+    if args.simplify is not None:
+        result = simplified(args, result)
     write_formats(paths, formats, result, args.colour)
     if picked is not None:
         guides, binding = picked
+        if args.simplify is not None:                                              # the guides as they are written: chosen before, simplified with the rest
+            from scene.strand_simplify import take_strands
+            guides = take_strands(result, binding["guide_strand"])
         guide_paths = {f: "_guides".join(os.path.splitext(p)) for f, p in paths.items()}
         write_formats(guide_paths, formats, guides, args.colour)
         paths = dict(paths, **{f + "_guides": p for f, p in guide_paths.items()})

@@ -120,6 +120,7 @@ SIGNATURES = {
                              vp]),
     "hgs_strand_rejoin": (ci, [vp, ci, vp, C.c_longlong, vp, vp, ci, vp, ci, vp, vp, ci, vp, C.c_longlong, vp, vp]),
     "hgs_strand_smooth": (ci, [vp, ci, vp, C.c_longlong, vp, ci, ci, C.c_double, C.c_double, ci, C.c_double, vp, vp, vp]),
+    "hgs_strand_simplify": (ci, [vp, ci, vp, C.c_longlong, vp, ci, C.c_double, vp, vp, vp]),
     "hgs_guides_assign": (ci, [vp, ci, ci, ci, C.c_longlong, vp, vp, ci, vp, vp, vp, vp, vp]),
     "hgs_guides_update": (ci, [vp, ci, ci, ci, C.c_longlong, vp, ci, vp, C.c_longlong, vp, vp, vp]),
     "hgs_guides_pick": (ci, [vp, ci, ci, vp, C.c_longlong, vp, vp, vp]),

@@ -1065,6 +1065,26 @@ int hgs_strand_rejoin(void* stream, int K, const long long* offsets, long long P
 int hgs_strand_smooth(void* stream, int K, const long long* offsets, long long P, const float* points, int max_joints, int iters,
                       double lam, double mu, int has_max_move, double max_move, float* out_points, int* status, int* clamped);
 
+/* hgs_strand_simplify (csrc/hgs_strand_simplify.hip) <-> exported strands simplified to a tolerance (scene/strand_simplify.py states
+ *   the contract and has the numpy path; export_strands.py --simplify; the reference has nothing of the kind).  Added under ABI 15.
+ *   Douglas-Peucker with the distance to the segment, per strand.  Strands as for hgs_strand_smooth: K strands over points [P][3]
+ *   float32 through offsets [K + 1] int64 (the caller's duty; a range that does not lie inside the P points counts as a strand
+ *   without joints).  Per strand with joints p_0 .. p_{n-1}, float64, one rounding per operation, dot(u, v) = (u0*v0 + u1*v1) + u2*v2:
+ *     n < 3: status 1 (short).  n > max_joints: status 2 (long).  Any coordinate not finite: status 3.  Every joint is kept, rounds 0.
+ *     Otherwise status 0.  d2(p; a, b): ab = b - a, ap = p - a, L2 = dot(ab, ab), t = dot(ap, ab) / L2 where L2 > 0, else 0, clamped
+ *     to [0, 1]; q_c = ap_c - t*ab_c; d2 = dot(q, q).  Joints 0 and n - 1 are kept; the interval (0, n - 1) has depth 1.  In an interval
+ *     (i, k) of consecutive kept joints with k > i + 1 the joint j* of the largest d2(p_j; p_i, p_k), the smallest j among equals, is
+ *     kept if d2 > tol*tol (strict; the product is formed once), and (i, j*) and (j*, k), of the next depth, are treated alike.
+ *     rounds[s] = the largest depth at which a joint was kept.
+ *   tol is finite and >= 0.  max_joints (3 to 1024): the number of joints of the launch's longest strand with 3 <= n <= 1024, which
+ *   the caller reads off the offsets; 0 where there is none (every strand of 3 joints or more is then long).  It sizes the dynamic
+ *   LDS -- one wavefront per strand keeps the strand in 48 * max_joints + 128 bytes, 4, 2 or 1 wavefronts a workgroup, whichever is
+ *   the most that fits 64 KB.  keep [P] uint8 is written for every joint of every strand (1: kept); status, rounds [K] int32.  Integer
+ *   LDS atomics on exact keys only: bitwise reproducible.  Bad sizes, tol or max_joints and, for K > 0, null or aliased pointers
+ *   return 1 before anything is launched; K == 0 returns 0. */
+int hgs_strand_simplify(void* stream, int K, const long long* offsets, long long P, const float* points, int max_joints, double tol,
+                        unsigned char* keep, int* status, int* rounds);
+
 /* hgs_guides_assign / hgs_guides_update / hgs_guides_pick (csrc/hgs_guides.hip) <-> guide strands picked from an exported groom by
  *   Lloyd's k-means (scene/strand_guides.py states the contract and has the numpy path; export_strands.py --select_guides).  N strands
  *   of M >= 2 points each, points float32 [n_points][3] with N*M <= n_points; strand i's feature is its S sampled points
