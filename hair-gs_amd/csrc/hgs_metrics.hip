@@ -185,10 +185,11 @@ __global__ __launch_bounds__(MT_BLOCK) void oriented_match_kernel(int nA, MatchP
 }
 
 #define VOTE_EMPTY64 0xFFFFFFFFFFFFFFFFull
-#define VOTE_EMPTY32 0xFFFFFFFFu
 
 // one workgroup per A strand s (its points a_pts[offsets[s] .. offsets[s+1]), strand order).  LDS: the (point, B strand) set
-// (keys, pair masks) and the B strand count table (keys, counts), `cap` entries each (a power of two).
+// (keys, pair masks) and the B strand count table, `cap` entries each (a power of two).  A count slot is one 64-bit word,
+// the B strand number above its count, claimed as (number, 0): every bit pattern of a strand number is a key, and an empty
+// slot is told apart by its count bits, all ones, which no count (<= cap) reaches.
 __global__ __launch_bounds__(MT_BLOCK) void strand_votes_kernel(int S, MatchParams P, const double* __restrict__ a_pts,
                                                                 const double* __restrict__ a_dirs, const long long* __restrict__ offsets,
                                                                 const int* __restrict__ b_strand, const uint32_t* __restrict__ starts,
@@ -197,9 +198,8 @@ __global__ __launch_bounds__(MT_BLOCK) void strand_votes_kernel(int S, MatchPara
                                                                 int* __restrict__ overflow, int* __restrict__ n_overflow) {
   extern __shared__ unsigned long long lds_words[];
   unsigned long long* set_key = lds_words;
-  uint32_t* set_val = (uint32_t*)(set_key + cap);
-  uint32_t* cnt_key = set_val + cap;
-  uint32_t* cnt_val = cnt_key + cap;
+  unsigned long long* cnt = set_key + cap;
+  uint32_t* set_val = (uint32_t*)(cnt + cap);
   __shared__ int s_flag, s_max;
   const int s = blockIdx.x;
   const long long p0 = offsets[s], n = offsets[s + 1] - p0;
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(MT_BLOCK) void strand_votes_kernel(int S, MatchPara
     return;
   }
   for (int k = 0; k < P.K; k++) {
-    for (int t = threadIdx.x; t < cap; t += MT_BLOCK) { cnt_key[t] = VOTE_EMPTY32; cnt_val[t] = 0u; }
+    for (int t = threadIdx.x; t < cap; t += MT_BLOCK) cnt[t] = VOTE_EMPTY64;
     __syncthreads();
     for (int t = threadIdx.x; t < cap; t += MT_BLOCK) {
       const unsigned long long key = set_key[t];
@@ -250,14 +250,15 @@ __global__ __launch_bounds__(MT_BLOCK) void strand_votes_kernel(int S, MatchPara
       const uint32_t bs = (uint32_t)key;
       uint32_t slot = (bs * 0x9E3779B1u) & cmask;   // distinct B strands <= set entries <= cap: always finds a slot
       for (;; slot = (slot + 1) & cmask) {
-        const uint32_t prev = atomicCAS(&cnt_key[slot], VOTE_EMPTY32, bs);
-        if (prev == VOTE_EMPTY32 || prev == bs) break;
+        const unsigned long long prev = atomicCAS(&cnt[slot], VOTE_EMPTY64, (unsigned long long)bs << 32);
+        if (prev == VOTE_EMPTY64 || (uint32_t)(prev >> 32) == bs) break;
       }
-      atomicAdd(&cnt_val[slot], 1u);
+      atomicAdd(&cnt[slot], 1ull);                  // (the count is the low word: at most cap, no carry into the number)
     }
     __syncthreads();
     int mx = 0;
-    for (int t = threadIdx.x; t < cap; t += MT_BLOCK) mx = max(mx, (int)cnt_val[t]);
+    for (int t = threadIdx.x; t < cap; t += MT_BLOCK)
+      if (cnt[t] != VOTE_EMPTY64) mx = max(mx, (int)(uint32_t)cnt[t]);
     atomicMax(&s_max, mx);
     __syncthreads();
     if (threadIdx.x == 0) { best[(size_t)k * S + s] = s_max; s_max = 0; }

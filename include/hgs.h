@@ -855,11 +855,13 @@ int hgs_scalp_votes(void* stream, long long N, const double* points, const doubl
  *   and dot(a_dir_i, b_dir_j) >= cos_k (|dot| when bidirectional; NaN never matches).  Builds a hashed grid of B in scratch
  *   (>= hgs_oriented_match_scratch_bytes(nB) bytes, 256-byte aligned), which hgs_strand_votes reads afterwards.
  * hgs_strand_votes: A's S strands are runs of its points, offsets[S+1] (int64); b_strand[nB] = a strand number per B point
- *   (only equality matters).  best[k][s] = max over B strands b of the number of points of strand s that some point of b
+ *   (only equality matters: any int, -1 and INT_MIN included).  best[k][s] = max over B strands b of the number of points of strand s that some point of b
  *   matches under pair k.  Needs the scratch of an hgs_oriented_match call with the same B, thresholds and box, left
  *   unchanged.  `capacity` (a power of two <= 2048) sizes the workgroup's LDS tables; a strand whose distinct (point,
  *   B strand) matches do not fit is appended to overflow[*n_overflow] (*n_overflow device, zero on entry) and its best[.][s]
- *   is left unwritten: the caller counts it. */
+ *   is left unwritten: the caller counts it.
+ * Empty sides: nA == 0 (S == 0) returns 0 and writes nothing; nB == 0 needs no B arrays and no scratch and zeroes mask
+ *   (best; overflow and *n_overflow stay as they are). */
 size_t hgs_oriented_match_scratch_bytes(int nB);
 int hgs_oriented_match(void* stream, int nA, int nB, int K, const double* a_pts, const double* a_dirs, const double* b_pts,
                        const double* b_dirs, const double* thresholds_host, int bidirectional, const double* box_host,
