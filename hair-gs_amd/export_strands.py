@@ -8,6 +8,7 @@ merge.py that the reference leaves to scripts/convert_output.py (MeshLab PLYs of
                            [--attach_roots [--attach_margin 0] [--attach_step S] [--attach_max_steps 256] [--attach_pull 1] [--attach_descent 0.25]
                             [--attach_max_distance D] [--attach_field PATH] [--attach_min_conf 0.5] [--attach_scalp_distance D] [--drop_unattached]]
                            [--smooth_strands [--smooth_iters 10] [--smooth_lambda 0.5] [--smooth_mu -0.53] [--smooth_max_move D]]
+                           [--dedupe DIST]
                            [--select_guides K [--select_samples 16] [--select_iters 10]]
                            [--simplify TOL]
 A model directory is read at its newest point_cloud/iteration_N (utils/system.py model_ply, as eval.py reads it); the SH degree is read off the file.  Every
@@ -79,7 +80,17 @@ roots and tips are always kept, strands of fewer than 3 or more than 1024 joints
 alone and counted, and attributes are not looked at: the line `Simplified strands (tol ...): ...` says how many joints are left, how
 many a strand keeps, the rounds taken, the largest deviation of a dropped joint and, per attribute, how far a dropped joint's value
 was from linear between the kept joints around it.  It works with --points 0 too.  Without the flag the strands are written as they
-are."""
+are.
+--dedupe DIST drops the near copies among the strands that are written (scene/strand_dedupe.py: the contract): --interpolate gives a
+root that sits on a guide's root that guide back, and a trained model carries duplicated strands of its own, which a renderer pays for
+and shades darker than one.  A strand is dropped when an earlier strand that is itself kept has EVERY joint within DIST (scene units)
+of its own joint of the same index; earlier strands win, so the trained strands beat the interpolated ones.  It is the chain's only
+strand-to-strand step and runs after --interpolate and --resolve_head, before --select_guides (the k-means then clusters, and the
+binding indexes, the strands that are written) and --simplify; it compares joint by joint and needs a fixed number of points per
+strand (--points M > 0).  Kept strands keep every bit; strands with a coordinate that is not finite pair with nothing and stay.  The
+line `Deduplicated strands (dist ...): ...` says how many strands stay, the pairs found, the rounds the resolution took, how many
+kept strands replace others and the most one replaces.  A DIST that pairs more than 2^27 times glues the groom together and is refused.
+Without the flag the strands are written as they are."""
 import os
 import sys
 
@@ -222,6 +233,16 @@ def smoothed(args, strands):
     return out
 
 
+def deduplicated(args, strands):
+    """--dedupe: the strands without their near copies (scene/strand_dedupe.py), and what that did."""
+    from scene.strand_dedupe import dedupe_strands
+    out, rep = dedupe_strands(strands, args.dedupe, device=None if args.device == "cpu" else args.device)
+    print(f"Deduplicated strands (dist {args.dedupe:g}): {rep['kept']} of {rep['strands']} strands kept, {rep['dropped']} dropped "
+          f"({rep['nonfinite']} not finite, which pair with nothing); {rep['pairs']} pairs, {rep['rounds']} rounds; {rep['groups']} kept strands "
+          f"replace others, at most {rep['largest_group']} each; joints {rep['joints_before']} -> {rep['joints_after']}")
+    return out
+
+
 def selected(args, strands):
     """--select_guides: (guide strands, binding) of the strands that are written (scene/strand_guides.py), and what that did."""
     from scene.strand_guides import select_guides
@@ -306,7 +327,17 @@ def main(argv=None):
     parser.add_argument("--select_samples", type=int, default=16, help="with --select_guides: joints compared per strand (2 to 64)")
     parser.add_argument("--select_iters", type=int, default=10, help="with --select_guides: assignments at most (1 to 256)")
     parser.add_argument("--simplify", type=float, default=None, metavar="TOL", help="drop every joint within TOL (scene units) of the chord that replaces it; runs last")
+    parser.add_argument("--dedupe", type=float, default=None, metavar="DIST", help="drop every strand whose joints all lie within DIST (scene units) of an earlier kept strand's")
     args = parser.parse_args(argv)
+    if args.dedupe is not None:
+        from scene.strand_dedupe import check_parameters as check_dedupe
+        try:
+            check_dedupe(args.dedupe)
+        except ValueError as e:
+            parser.exit(2, f"export_strands.py: --dedupe: {e}\n")
+        if args.points <= 0:
+            parser.exit(2, "export_strands.py: --dedupe compares strands joint by joint and needs a fixed number of points per strand: "
+                           "--points M > 0 is needed (--points 0, the joints themselves, cannot be combined with it)\n")
     if args.select_guides is not None:
         from scene.strand_guides import check_parameters as check_select
         try:
@@ -381,6 +412,12 @@ def main(argv=None):
         result = interpolated(args, model, result)
     if args.resolve_head:
         result = resolved(args, field, result)
+    if args.dedupe is not None:
+        from hgs_runtime import HgsError
+        try:
+            result = deduplicated(args, result)
+        except (ValueError, HgsError) as e:
+            parser.exit(2, f"export_strands.py: --dedupe: {e}\n")
     paths = output_paths(args.output, formats)
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     picked = None

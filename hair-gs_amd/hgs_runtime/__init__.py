@@ -124,6 +124,9 @@ SIGNATURES = {
     "hgs_guides_assign": (ci, [vp, ci, ci, ci, C.c_longlong, vp, vp, ci, vp, vp, vp, vp, vp]),
     "hgs_guides_update": (ci, [vp, ci, ci, ci, C.c_longlong, vp, ci, vp, C.c_longlong, vp, vp, vp]),
     "hgs_guides_pick": (ci, [vp, ci, ci, vp, C.c_longlong, vp, vp, vp]),
+    "hgs_dedupe_count": (ci, [vp, ci, ci, C.c_longlong, vp, C.c_double, vp]),
+    "hgs_dedupe_fill": (ci, [vp, ci, ci, C.c_longlong, vp, C.c_double, vp, C.c_longlong, vp]),
+    "hgs_dedupe_resolve": (ci, [vp, ci, vp, C.c_longlong, vp, vp, vp, ci, vp, vp, vp]),
     "hgs_field_splat": (ci, [vp, ci, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, C.c_double, vp, vp]),
     "hgs_field_solve": (ci, [vp, ci, ci, ci, vp, vp, vp]),
     "hgs_strand_trace": (ci, [vp, ci, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, C.c_double, ci,
@@ -258,6 +261,7 @@ class BlockPlan(C.Structure):
 PARAMS_HAIR, PARAMS_CLOUD = 1, 2
 HEAD_SKIP_PIXELS, HEAD_SKIP_SMOOTH = 1, 2
 VIEW_QUEUE_MAX = 16   # include/hgs.h HGS_VIEW_QUEUE_MAX
+DEDUPE_PARTS = 8      # include/hgs.h HGS_DEDUPE_PARTS
 HEAD_OUT = ["total", "l1", "dssim", "mask", "orientation", "smooth", "ori_count", "smooth_count", "g_ssim", "g_l1", "g_mask",
             "g_ori", "g_smooth", "total_fwd"]
 HEAD_NOUT = 16

@@ -1108,6 +1108,33 @@ int hgs_guides_update(void* stream, int N, int M, int S, long long n_points, con
 int hgs_guides_pick(void* stream, int N, int K, const long long* order, long long n_order, const long long* start, const double* dist2,
                     long long* guide);
 
+/* hgs_dedupe_count / hgs_dedupe_fill / hgs_dedupe_resolve (csrc/hgs_dedupe.hip) <-> near-copy strands dropped from an exported groom
+ *   (scene/strand_dedupe.py states the contract and has the numpy path; export_strands.py --dedupe; the reference has nothing of the
+ *   kind).  Added under ABI 15.  N strands of M >= 2 points each, points float32 [n_points][3] with N*M <= n_points.  All arithmetic
+ *   is float64, one rounding per operation in the order written.  pair(i, j), i != j, holds iff (dx*dx + dy*dy) + dz*dz <= tol*tol
+ *   (the product formed once) at EVERY joint s = 0 .. M-1, d = x_i[s] - x_j[s]; a coordinate that is not finite makes the comparison
+ *   false.  tol is finite and >= 0.  Every argument is checked before anything is launched; N == 0 returns 0.
+ * hgs_dedupe_count: counts [N][HGS_DEDUPE_PARTS] int32; counts[i][c] = the j < i with pair(i, j) among the strands of part c: the
+ *   strands below the last strand of i's block of 256 are cut, in tiles of 256, into HGS_DEDUPE_PARTS contiguous parts of ascending j,
+ *   a workgroup each.  Row i sums to strand i's lower neighbours.
+ * hgs_dedupe_fill: starts [N*HGS_DEDUPE_PARTS] int64 = the exclusive prefix sum of the flattened counts (so starts[i*HGS_DEDUPE_PARTS]
+ *   is strand i's lower_offsets), n_pairs their total; lower [n_pairs] int32 gets every strand's lower neighbours, ascending in j.  tol
+ *   and the points must be the count pass's; a list that does not match is truncated at its slot's end, never overrun.  n_pairs == 0
+ *   returns 0.  No atomics: the same bytes on every run.
+ * hgs_dedupe_resolve: one Jacobi round of "a strand is kept unless a kept earlier strand pairs with it".  lower_offsets [N + 1]
+ *   int64 and lower [n_pairs] int32 as above (entries outside [0, i) and ranges outside [0, n_pairs] are skipped); state [N] uint8:
+ *   0 undecided, 1 kept, 2 dropped.  A strand that is undecided in `state` and whose lower neighbours are all decided there gets, in
+ *   state_out, 2 with kept_by [N] int64 = its smallest kept lower neighbour, or 1 with kept_by = itself where none is kept, and
+ *   rounds [N] int32 = round (>= 1); every other strand's state is copied and its kept_by and rounds are left alone.  undecided [1]
+ *   int32 is ADDED the number of strands undecided in state_out (an integer atomic per wavefront; the caller zeroes it).  state_out
+ *   must not be state; no output may alias another buffer. */
+#define HGS_DEDUPE_PARTS 8
+int hgs_dedupe_count(void* stream, int N, int M, long long n_points, const float* points, double tol, int* counts);
+int hgs_dedupe_fill(void* stream, int N, int M, long long n_points, const float* points, double tol, const long long* starts,
+                    long long n_pairs, int* lower);
+int hgs_dedupe_resolve(void* stream, int N, const long long* lower_offsets, long long n_pairs, const int* lower, const unsigned char* state,
+                       unsigned char* state_out, int round, long long* kept_by, int* rounds, int* undecided);
+
 /* Strands traced from the scalp through the lifted hair directions (csrc/hgs_trace.hip; utils/trace.py states the contract and has
  *   the numpy paths).  All float64, one rounding per operation.  Every argument is checked before a pointer is touched.  The grid:
  *   node (ix, iy, iz) lies at origin + index * h, 2 <= n <= 1024 an axis, at most 2^26 nodes in all.
